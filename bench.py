@@ -32,6 +32,16 @@ back and consecutive frames overlap on the GPU (pt_api.cpp's two-slot render
 pipeline: the next frame's waves fill the CUs the previous frame's drain
 leaves idle); config.single_frame_ms is the wall-clock time of one frame
 rendered alone, synchronised on both sides.
+
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline
+figure needs: scene load and upload, W warm-up frames, the N timed frames, the
+result line (metric, value, unit, ms_per_step, the launch's shape).  `--full`
+adds everything else the line can carry: the stats launches (counters,
+roofline), one frame alone (single_frame_ms) and the host-output path, the
+one-frame-per-launch rate, the companion workloads and the CPU baselines; at
+N > 1 the 1-GPU point of the curve (efficiency) and the multi-GPU companions.
+`--dump-outputs DIR` writes the frame of the last timed step as DIR/frame.npy
+(the inputs are the same in every run: deterministic scenes, fixed seed).
 """
 from __future__ import annotations
 
@@ -77,14 +87,33 @@ VALU_PEAK_GINST = 256 * 2 * 2.4
 L2_LINE = 128
 
 
+def scene_cache_dir() -> str:
+    """Where the generated scenes (and the CPU baselines' scene dump) are kept:
+    <repository>/_scenes, or, when this user cannot write there (a read-only
+    tree), a directory of this user's under the system's temporary directory.
+    The scenes are deterministic: the same bytes wherever they are written."""
+    import tempfile
+    d = os.path.join(ROOT, "_scenes")
+    try:
+        os.makedirs(d, exist_ok=True)
+        if os.access(d, os.W_OK | os.X_OK):
+            return d
+    except OSError:
+        pass
+    d = os.path.join(tempfile.gettempdir(), f"dsgpuraytracing_amd_scenes_{os.getuid()}")
+    os.makedirs(d, mode=0o700, exist_ok=True)
+    return d
+
+
 def workload_scene(wl):
     from dsgpuraytracing_amd import scenes
+    cd = scene_cache_dir()
     if wl["scene"] == "sub1":
-        dae, envmap = scenes.proxy_path(1), None
+        dae, envmap = scenes.proxy_path(1, cd), None
     elif wl["scene"] == "c5":
-        dae, envmap = scenes.c5_path(2), scenes.c5_envmap_path()
+        dae, envmap = scenes.c5_path(2, cd), scenes.c5_envmap_path(cd)
     elif wl["scene"] == "c5big":
-        dae, envmap = scenes.c5_path(3), scenes.c5_envmap_path()
+        dae, envmap = scenes.c5_path(3, cd), scenes.c5_envmap_path(cd)
     else:
         dae, envmap = scenes.C1_DAE, None
     cam = os.path.join(ROOT, "assets", wl["cam"]) if wl.get("cam") else None
@@ -315,10 +344,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the launch counters and the roofline (stats launches "
+                         "of their own), one frame alone and the host-output path, the companion workloads "
+                         "(--no-extras drops them) and the CPU baselines (--no-cpu-baseline drops them); N > 1: the "
+                         "1-GPU point of the curve and the companions.  A plain run sets up, warms up, times the "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame the last timed step rendered (what a caller of the "
+                         "timed path receives: H x W x 3 float32 radiance) as DIR/frame.npy")
     ap.add_argument("--scene-dump", default=None, help="PTDUMP scene instead of the native .dae loader")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the companion measurements (N = 1: framed C3, single-GPU C4 and C5, host-SAH tree, "
+                    help="with --full: skip the companion measurements (N = 1: framed C3, single-GPU C4 and C5, host-SAH tree, "
                          "per-tile seams; N > 1: the C4 frame split and the weak C3 pass)")
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="default: c3 (the headline config) at every N")
@@ -351,6 +389,8 @@ def main():
                          "(default; BASELINE C4: --workload c4); weak = one pass of the whole frame per GPU over "
                          "disjoint sample ranges + one RCCL reduce")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps needs at least one timed step, --warmup none or more")
     if os.environ.get("PT_BENCH_LBVH") == "1":  # A/B arms (tools/ab.sh): the GPU-built tree
         args.lbvh = True
 
@@ -536,10 +576,14 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
             done += m
 
     # counters for the roofline's algorithmic bytes: the reference's binary BVH
-    # (SURVEY.md §8(d) cost model); and the launch's own counters (4-wide BVH)
-    st_counts = step(stats="ref")
-    st_perf = step(stats=True)
-    guard.check()
+    # (SURVEY.md §8(d) cost model); and the launch's own counters (4-wide BVH).
+    # Stats launches of their own: --full, and N > 1 (the footprint, the
+    # ranks' sample grouping and the per-rank fields come from them)
+    st_counts = st_perf = None
+    if args.full or world > 1:
+        st_counts = step(stats="ref")
+        st_perf = step(stats=True)
+        guard.check()
     if weak:
         # Rows outside the scene's screen footprint are 0 in every pass (their
         # camera rays miss the scene box: pt_stats.footprint), so the reduce
@@ -552,7 +596,7 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
         frame[:y0].zero_()
         frame[y1 + 1:].zero_()
     # the ranks must group each pixel's samples alike (bit-identical frame)
-    knobs = check_value_knobs({"group_spp": st_perf["group_spp"]})
+    knobs = check_value_knobs({"group_spp": st_perf["group_spp"]}) if st_perf is not None else None
     steps(args.warmup)
     guard.check()
     if world > 1:
@@ -567,6 +611,12 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     guard.check()
+    if knobs is None:  # (one GPU, plain run: the grouping the timed launches chose)
+        knobs = check_value_knobs({"group_spp": s_get(dev, "group_spp")})
+    # the frame of the last timed step, before anything else renders into it
+    last_frame = frame.float().cpu().numpy() if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"frame": last_frame})
     # HIP events recorded around every launch on its stream (the timed ones)
     n_launch = args.steps if fpl <= 1 or weak else -(-args.steps // fpl)
     kernel_ms, resolve_ms = dev.launch_times(n_launch)
@@ -578,7 +628,7 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
     # strong split: the 1-GPU point of the curve, rank 0 rendering the whole
     # frame alone behind a barrier (the other ranks idle), same clock and frames
     rate1, shared = None, False
-    if world > 1 and not weak:
+    if world > 1 and not weak and args.full:
         rate1, shared = single_gpu_rate(dev, tiles, W, H, SPP, frame, stream, rank, backend, args.steps, fpl=fpl)
     per_rank = None
     if world > 1:
@@ -594,7 +644,7 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
         per_rank = [[round(float(v), 4) for v in r.cpu().tolist()] for r in allr]
 
     multi = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and args.full and not args.no_extras:
         # every rank takes part (collectives inside)
         multi = multi_gpu_companions(local, rank, world, backend, StepGuard, PipelinedExchange,
                                      frames=max(3, min(args.steps, 10)), with_weak=not weak,
@@ -606,7 +656,7 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
     frame_batch = None
     iso_ms = 0.0
     iso_single_ms = None
-    if world == 1:
+    if world == 1 and args.full:
         # one frame alone, synchronised on both sides (no overlap with a
         # neighbouring frame): the wall-clock render time of ONE frame, and
         # the render kernel's own duration (HIP events around a launch that
@@ -671,7 +721,7 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
         if args.emulate_shard > 1:
             value = float(np.sum(mine_arr[:, 2] * mine_arr[:, 3])) * SPP * frames / elapsed / 1e6
         avg_ms = float(np.mean(kernel_ms))
-        img = frame.float().cpu().numpy()
+        img = last_frame
         # at N = 1 the line names the curve it starts (the driver's N > 1 runs
         # use the same default, the C3 frame split)
         scaling = "weak" if weak else "strong" if world > 1 else args.scaling
@@ -684,6 +734,7 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
             "warmup": args.warmup,
             "ms_per_step": round(elapsed / frames * 1e3, 3),
             "higher_is_better": True,
+            "full": bool(args.full),
             "scaling": scaling,
             "vs_baseline": None,
             "dtype": "fp32",
@@ -719,17 +770,7 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
                        "bvh": bvh_desc(args.lbvh),
                        "upload_s": round(t_up, 4),
                        "host_output_ms_per_frame": None if host_ms is None else round(host_ms, 3)},
-            "roofline": roofline(workload, elapsed / frames * 1e3, algorithmic_bytes(st_counts), isolated_ms=iso_ms,
-                                 pipelined_ms=avg_ms, lib_sha=lib_sha256(), kernel_sha=kernel_sha256()),
             "resolve_ms": round(float(np.mean(resolve_ms)), 4),
-            "counters": {k: st_counts[k] for k in ("camera_rays", "bounce_rays", "shadow_rays", "node_visits",
-                                                   "tri_tests", "sphere_tests", "ext_hits", "culled_samples")},
-            "launch_counters": {k: st_perf[k] for k in ("node_visits", "tri_tests", "sphere_tests", "wave_trav_steps",
-                                                        "leaf_steps", "wave_rounds", "queue_atomics", "shade_clocks",
-                                                        "hitshade_clocks", "trav_clocks", "max_wave_clocks",
-                                                        "wave_wall_sum", "wave_wall_max", "section_clocks", "wave_span",
-                                                        "lane_iters", "partial_bytes", "deep_stack_steps",
-                                                        "node_census")},
             # frames per timed launch: the roofline's counts and durations are per
             # frame; one launch of the kernel trace = launch_ms, frames_per_launch frames
             "launch": {"frames_per_launch": fpl, "launch_ms": round(avg_ms * (args.steps / n_launch), 4),
@@ -740,21 +781,18 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
                        "group_spp": s_get(dev, "group_spp")},
             "image_mean": float(img.mean()),
         }
-        rays = st_counts["camera_rays"] + st_counts["bounce_rays"] + st_counts["shadow_rays"]
-        out["ray_casts_per_s_M"] = round(rays * frames * (world if weak else 1) / elapsed / 1e6, 1)
-        # The rates a reader needs beside `value`: samples
-        # actually traced (the footprint cull's samples excluded; a strong
-        # split sums its ranks' culls), and one frame alone (no overlap with a
-        # neighbouring frame: W*H*spp / single_frame_ms)
-        culled = (sum(r[5] for r in per_rank) if (per_rank and not weak) else
-                  st_counts["culled_samples"] * (world if weak else 1))
-        out["traced_samples_per_s_M"] = round((W * H * SPP * (world if weak else 1) - culled) * frames / elapsed / 1e6, 1)
+        if st_counts is not None:
+            counted_rates(out, st_counts, st_perf, per_rank, frames, elapsed, world, weak)
+        if args.full:
+            out["roofline"] = roofline(workload, elapsed / frames * 1e3, algorithmic_bytes(st_counts), isolated_ms=iso_ms,
+                                       pipelined_ms=avg_ms, lib_sha=lib_sha256(), kernel_sha=kernel_sha256())
+            # the graded kernel fraction: the isolated launch's VALU-issue fraction
+            vv = out["roofline"]["views"].get("valu")
+            out["roofline"]["frac_kernel"] = vv.get("frac_isolated") if vv else None
+        # one frame alone (no overlap with a neighbouring frame: W*H*spp / single_frame_ms)
         out["single_frame_Mrays"] = None if single_ms is None else round(W * H * SPP / (single_ms * 1e-3) / 1e6, 1)
         if frame_batch is not None:
             out["one_frame_per_launch"] = frame_batch
-        # the graded kernel fraction: the isolated launch's VALU-issue fraction
-        vv = out["roofline"]["views"].get("valu")
-        out["roofline"]["frac_kernel"] = vv.get("frac_isolated") if vv else None
         if per_rank is not None:
             out["per_rank"] = {"fields": ["kernel_ms", "resolve_ms", "exchange_ms", "pixels", "partial_bytes",
                                           "culled_samples"],
@@ -776,19 +814,18 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
                 out["kernel_ms_slowest_over_mean"] = round(max(kms) / max(1e-9, float(np.mean(kms))), 4)
         if multi is not None:
             out["companions"] = multi
-        if world == 1 and not args.no_extras and workload == "c3" and not args.scene_dump:
+        if world == 1 and args.full and not args.no_extras and workload == "c3" and not args.scene_dump:
             out["companions"] = companions(dev, local, stream, max(2, min(args.steps, 5)))
         out["dist"] = {"backend": backend if world > 1 else None,
                        "world_size": dist.get_world_size() if dist.is_initialized() else 1,
                        "timeout_s": float(os.environ.get("PT_DIST_TIMEOUT", "120")) if world > 1 else None,
                        "value_knobs": knobs}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 dp = dump_path
                 if dp is None:
                     from dsgpuraytracing_amd import scene_loader
-                    os.makedirs(os.path.join(ROOT, "_scenes"), exist_ok=True)
-                    dp = os.path.join(ROOT, "_scenes", f"bench_{workload}.ptd")
+                    dp = os.path.join(scene_cache_dir(), f"bench_{workload}.ptd")
                     scene_loader.dump_dae(dae, W, H, dp, cam_info=cam, envmap=envmap)
                 if dae is not None and os.access(REF_DRIVER, os.X_OK) and cam is None:
                     out["cpu_baseline"] = cpu_baseline_reference(dae, envmap)
@@ -800,6 +837,43 @@ def bench_run(args, backend, local, rank, world, StepGuard, PipelinedExchange, c
             except Exception as e:  # reported, never silently replaced
                 out["cpu_baseline"] = {"error": repr(e)}
         print(json.dumps(out), flush=True)
+
+
+def counted_rates(out, st_counts, st_perf, per_rank, frames, elapsed, world, weak):
+    """The line's fields that come from the stats launches' counters."""
+    out["counters"] = {k: st_counts[k] for k in ("camera_rays", "bounce_rays", "shadow_rays", "node_visits",
+                                                 "tri_tests", "sphere_tests", "ext_hits", "culled_samples")}
+    out["launch_counters"] = {k: st_perf[k] for k in ("node_visits", "tri_tests", "sphere_tests", "wave_trav_steps",
+                                                      "leaf_steps", "wave_rounds", "queue_atomics", "shade_clocks",
+                                                      "hitshade_clocks", "trav_clocks", "max_wave_clocks",
+                                                      "wave_wall_sum", "wave_wall_max", "section_clocks", "wave_span",
+                                                      "lane_iters", "partial_bytes", "deep_stack_steps",
+                                                      "node_census")}
+    rays = st_counts["camera_rays"] + st_counts["bounce_rays"] + st_counts["shadow_rays"]
+    out["ray_casts_per_s_M"] = round(rays * frames * (world if weak else 1) / elapsed / 1e6, 1)
+    # The rate a reader needs beside `value` (VERDICT r5 item 7): samples
+    # actually traced (the footprint cull's samples excluded; a strong
+    # split sums its ranks' culls)
+    culled = (sum(r[5] for r in per_rank) if (per_rank and not weak) else
+              st_counts["culled_samples"] * (world if weak else 1))
+    out["traced_samples_per_s_M"] = round((W * H * SPP * (world if weak else 1) - culled) * frames / elapsed / 1e6, 1)
+
+
+DUMP_LIMIT_BYTES = 60_000_000  # (below the 64 MB a dump may take, .npy headers included)
+
+
+def dump_outputs(outdir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as <outdir>/<name>.npy (float32), under
+    64 MB in all; a larger array is stored as a fixed, seeded sample of its
+    elements (in index order), the same sample in every run."""
+    os.makedirs(outdir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > budget:
+            pick = np.sort(np.random.RandomState(12345).choice(a.size, budget // 4, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(outdir, f"{name}.npy"), a)
 
 
 def device_fingerprint(local: int) -> str:

@@ -187,12 +187,12 @@ _MIRROR_SPHERE_NODE = """      <node id="MirrorSphere" name="MirrorSphere" type=
 """
 
 
-def make_c5(levels: int, dst: str) -> str:
+def make_c5(levels: int, dst: str, cache_dir: Optional[str] = None) -> str:
     """C5 proxy: CBbunny_sub<levels> with the bunny's
     material switched to <glass> (ior 1.45, the commented template of
     CBspheres_lambertian.dae) and one <mirror> sphere (r = 0.25, resting on
     the floor beside the bunny, in CBspheres.dae's chrome syntax)."""
-    txt = open(proxy_path(levels)).read()
+    txt = open(proxy_path(levels, cache_dir)).read()  # (the proxy beside its C5 variant)
     e0 = txt.index('<effect id="Default-effect">')
     e1 = txt.index("</effect>", e0)
     txt = txt[:e1] + _GLASS_EXTRA + "    " + txt[e1:]
@@ -215,7 +215,7 @@ def c5_path(levels: int = 2, cache_dir: Optional[str] = None) -> str:
     cache_dir = cache_dir or os.path.join(ROOT, "_scenes")
     dst = os.path.join(cache_dir, f"CBbunny_sub{levels}_c5.dae")
     if not os.path.exists(dst) or os.path.getmtime(dst) < os.path.getmtime(__file__):
-        make_c5(levels, dst)
+        make_c5(levels, dst, cache_dir)
     return dst
 
 

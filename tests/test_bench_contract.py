@@ -148,6 +148,23 @@ def test_round6_line_reports_the_honest_rates():
     assert len(n) == 8 and n[0] > 0 and 0 <= n[1] <= n[0] and n[2] <= n[3]
 
 
+def test_dump_outputs_writes_float32_arrays_and_samples_large_ones(tmp_path, monkeypatch):
+    """--dump-outputs: <name>.npy in float32; an array over the budget is
+    stored as the same seeded sample of its elements in every run."""
+    import numpy as np
+    frame = np.arange(6 * 5 * 3, dtype=np.float64).reshape(6, 5, 3)
+    bench.dump_outputs(str(tmp_path / "a"), {"frame": frame})
+    got = np.load(tmp_path / "a" / "frame.npy")
+    assert got.dtype == np.float32 and got.shape == frame.shape and (got == frame).all()
+    assert bench.DUMP_LIMIT_BYTES < 64 * 10**6
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 40 * 4)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"frame": frame})
+    b, c = np.load(tmp_path / "b" / "frame.npy"), np.load(tmp_path / "c" / "frame.npy")
+    assert b.dtype == np.float32 and b.shape == (40,) and (b == c).all()
+    assert (np.diff(b) > 0).all() and set(b.tolist()) <= set(frame.reshape(-1).tolist())  # distinct elements, in order
+
+
 def test_round6_line_reports_its_frames_per_launch():
     """The C3 line renders its frames eight per launch (frame batches,
     pt_render_frames_device; bit-identical images) and says so -- config and

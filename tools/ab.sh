@@ -14,7 +14,7 @@ mkdir -p gpurun_out
 for r in $(seq 1 "$R"); do
   for v in "$@"; do
     IFS=, read -r lib envs <<< "$v"
-    out=$(env PT_LIB="$lib" ${envs//,/ } timeout -k 10 300 python bench.py --workload "$WL" --no-cpu-baseline --no-extras --steps 10 --warmup 2 2>/dev/null) || { echo "FAILED $v"; exit 3; }
+    out=$(env PT_LIB="$lib" ${envs//,/ } timeout -k 10 300 python bench.py --workload "$WL" --full --no-cpu-baseline --no-extras --steps 10 --warmup 2 2>/dev/null) || { echo "FAILED $v"; exit 3; }
     line=$(echo "$out" | tail -n 1)
     [ -n "$AB_FULL" ] && echo "{\"variant\": \"$v\", \"line\": $line}" >> "gpurun_out/ab_full_$WL.jsonl"
     echo "$v $(echo "$line" | AB_FULL="$AB_FULL" python -c '
