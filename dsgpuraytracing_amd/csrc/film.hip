@@ -1,0 +1,184 @@
+// film.hip — the device-resident progressive film: accumulate a pass, resolve
+// to the HDR mean / the RGBA8 toColor codes / the per-pixel error, and the
+// per-tile maximum of that error (include/ptgpu.h: pt_film_*), plus
+// pt_to_color_device, which shares the resolve's tonemap.
+//
+// The film arithmetic is a definition (ptgpu.h), restated in numpy by
+// tests/film_helpers.py and compared bit for bit: every operation is one
+// separately rounded IEEE f32 operation, so this translation unit is built
+// without fast-math and with contraction off (x*y+z would become v_fma_f32);
+// `/` and sqrtf are the correctly rounded sequences.
+//
+// Launch shape, as resolve_kernel (pt_kernels.hip): one 256-thread workgroup
+// per <= 32x32 tile, lane = pixel of a 32-pixel row, so each record plane and
+// each output is read or written as whole contiguous rows (16 B per lane: one
+// dwordx4 per record).  The kernels stay small (VGPR and LDS figures in
+// DESIGN.md): they run beside the next pass's persistent render waves.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+
+#include "film.h"
+
+#pragma clang fp contract(off)
+
+namespace ptk {
+
+// HDRImageBuffer::toColor's 8-bit code of one channel, as the host's pt_to_color
+// (image_out.cpp) computes it: the code is a non-decreasing step function of
+// the float's bit pattern, so it is the number of thresholds thr[1..255] at or
+// below the bits (thr[0] = 0): the largest k with thr[k] <= bits, by an 8-step
+// branchless search of the table in LDS.  Sign bit set: the host's powf path
+// gives 0 for -0.0f and 255 (NaN -> 255) for everything else; a positive NaN's
+// bits lie above every threshold (255).
+__device__ __forceinline__ uint32_t to_color_code(const uint32_t* thr, float v) {
+  const uint32_t b = __float_as_uint(v);
+  uint32_t k = 0;
+#pragma unroll
+  for (uint32_t s = 128; s; s >>= 1) k += thr[k + s] <= b ? s : 0u;
+  return b == 0x80000000u ? 0u : k;  // (any other bits >= 2^31 are above every threshold: 255)
+}
+
+__device__ __forceinline__ uint32_t to_color_rgba(const uint32_t* thr, float r, float g, float b) {
+  return (255u << 24) + (to_color_code(thr, b) << 16) + (to_color_code(thr, g) << 8) + to_color_code(thr, r);
+}
+
+// Standard error of the pass-weighted mean luminance relative to the mean.
+__device__ __forceinline__ float film_error(uint32_t n, float mu, float M2, uint32_t k) {
+  if (k < 2u) return INFINITY;
+  return sqrtf((fmaxf(M2, 0.0f) / (float)n) / (float)(k - 1u)) / fmaxf(mu, PT_FILM_LUM_FLOOR);
+}
+
+__global__ __launch_bounds__(256) void film_accumulate_kernel(FilmAccArgs a) {
+  const int4 t = a.tiles[blockIdx.x];
+  const size_t plane = (size_t)a.W * (size_t)a.H;
+  const float w = (float)a.spp;
+  const int dx = (int)threadIdx.x & 31;
+  if (dx >= t.z) return;
+  for (int dy = (int)threadIdx.x >> 5; dy < t.w; dy += 8) {
+    const size_t p = (size_t)(t.x + dx) + (size_t)(t.y + dy) * (size_t)a.W;
+    const float* m = a.pass + 3 * p;
+    const float mr = m[0], mg = m[1], mb = m[2];
+    uint4 s = a.rec[p];
+    uint4 e = a.rec[plane + p];
+    s.x = __float_as_uint(__uint_as_float(s.x) + mr * w);
+    s.y = __float_as_uint(__uint_as_float(s.y) + mg * w);
+    s.z = __float_as_uint(__uint_as_float(s.z) + mb * w);
+    s.w += a.spp;
+    const float L = (0.2126f * mr + 0.7152f * mg) + 0.0722f * mb;  // Spectrum::illum
+    const float Wn = (float)s.w;
+    float mu = __uint_as_float(e.x);
+    const float d = L - mu;
+    mu = mu + d * (w / Wn);
+    e.x = __float_as_uint(mu);
+    e.y = __float_as_uint(__uint_as_float(e.y) + (w * d) * (L - mu));
+    e.z += 1u;
+    a.rec[p] = s;
+    a.rec[plane + p] = e;
+  }
+}
+
+// Whole frame, one workgroup per tile of the 32x32 grid.
+__global__ __launch_bounds__(256) void film_resolve_kernel(FilmResolveArgs a) {
+  __shared__ uint32_t s_thr[256];
+  if (a.rgba) {  // (uniform)
+    s_thr[threadIdx.x] = a.thr[threadIdx.x];
+    __syncthreads();
+  }
+  const int tx = (a.W + 31) >> 5;
+  const int x = (((int)blockIdx.x % tx) << 5) + ((int)threadIdx.x & 31);
+  const int y0 = ((int)blockIdx.x / tx) << 5;
+  if (x >= a.W) return;
+  const size_t plane = (size_t)a.W * (size_t)a.H;
+  const int y1 = min(y0 + 32, a.H);
+  for (int y = y0 + ((int)threadIdx.x >> 5); y < y1; y += 8) {
+    const size_t p = (size_t)x + (size_t)y * (size_t)a.W;
+    const uint4 s = a.rec[p];
+    if (a.hdr || a.rgba) {
+      float r = 0.0f, g = 0.0f, b = 0.0f;
+      if (s.w) {
+        const float n = (float)s.w;
+        r = __uint_as_float(s.x) / n;
+        g = __uint_as_float(s.y) / n;
+        b = __uint_as_float(s.z) / n;
+      }
+      if (a.hdr) {
+        float* o = a.hdr + 3 * p;
+        o[0] = r;
+        o[1] = g;
+        o[2] = b;
+      }
+      if (a.rgba) a.rgba[p] = to_color_rgba(s_thr, r, g, b);
+    }
+    if (a.err) {
+      const uint4 e = a.rec[plane + p];
+      a.err[p] = film_error(s.w, __uint_as_float(e.x), __uint_as_float(e.y), e.z);
+    }
+  }
+}
+
+// One workgroup per listed tile (any size): the maximum of the error over its
+// pixels, lanes reduced by shuffles, the four waves through LDS.  The error is
+// >= 0 or +inf; an empty tile gives 0.
+__global__ __launch_bounds__(256) void film_tile_error_kernel(FilmErrArgs a) {
+  __shared__ float s_max[4];
+  const int4 t = a.tiles[blockIdx.x];
+  const size_t plane = (size_t)a.W * (size_t)a.H;
+  float v = 0.0f;
+  for (int dy = (int)threadIdx.x >> 5; dy < t.w; dy += 8)
+    for (int dx = (int)threadIdx.x & 31; dx < t.z; dx += 32) {
+      const size_t p = (size_t)(t.x + dx) + (size_t)(t.y + dy) * (size_t)a.W;
+      const uint32_t n = a.rec[p].w;
+      const uint4 e = a.rec[plane + p];
+      v = fmaxf(v, film_error(n, __uint_as_float(e.x), __uint_as_float(e.y), e.z));
+    }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+  if (((int)threadIdx.x & 63) == 0) s_max[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) a.out[blockIdx.x] = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
+}
+
+// pt_to_color_device: one workgroup per 32x32 block of the rectangle.
+__global__ __launch_bounds__(256) void to_color_kernel(ToColorArgs a) {
+  __shared__ uint32_t s_thr[256];
+  s_thr[threadIdx.x] = a.thr[threadIdx.x];
+  __syncthreads();
+  const int tx = (a.x1 - a.x0 + 31) >> 5;
+  const int x = a.x0 + (((int)blockIdx.x % tx) << 5) + ((int)threadIdx.x & 31);
+  const int y0 = a.y0 + (((int)blockIdx.x / tx) << 5);
+  if (x >= a.x1) return;
+  const int y1 = min(y0 + 32, a.y1);
+  for (int y = y0 + ((int)threadIdx.x >> 5); y < y1; y += 8) {
+    const size_t p = (size_t)x + (size_t)y * (size_t)a.W;
+    const float* c = a.hdr + 3 * p;
+    a.rgba[p] = to_color_rgba(s_thr, c[0], c[1], c[2]);
+  }
+}
+
+}  // namespace ptk
+
+extern "C" hipError_t ptk_film_accumulate(const FilmAccArgs* a, int n_tiles, hipStream_t s) {
+  if (n_tiles <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ptk::film_accumulate_kernel, dim3(n_tiles), dim3(256), 0, s, *a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t ptk_film_resolve(const FilmResolveArgs* a, hipStream_t s) {
+  const int grid = ((a->W + 31) / 32) * ((a->H + 31) / 32);
+  hipLaunchKernelGGL(ptk::film_resolve_kernel, dim3(grid), dim3(256), 0, s, *a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t ptk_film_tile_error(const FilmErrArgs* a, int n_tiles, hipStream_t s) {
+  if (n_tiles <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ptk::film_tile_error_kernel, dim3(n_tiles), dim3(256), 0, s, *a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t ptk_to_color(const ToColorArgs* a, hipStream_t s) {
+  const int grid = ((a->x1 - a->x0 + 31) / 32) * ((a->y1 - a->y0 + 31) / 32);
+  if (grid <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ptk::to_color_kernel, dim3(grid), dim3(256), 0, s, *a);
+  return hipGetLastError();
+}

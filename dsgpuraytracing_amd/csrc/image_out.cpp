@@ -42,6 +42,7 @@ struct ToColor {
   std::vector<uint8_t> code0;    // code at each bucket's first float (buckets = bits >> 15, up to +inf)
   std::vector<uint32_t> inner;   // bits of the threshold inside the bucket (kNone: none)
   std::vector<uint8_t> direct_b; // 1: the bucket holds two thresholds -- powf there
+  uint32_t thr[256];             // thr[k]: bits of the smallest float whose code reaches k (thr[0] = 0)
   static constexpr uint32_t kInf = 0x7f800000u, kNone = 0xffffffffu;
 
   uint32_t direct(float s) const { return code8(std::pow(s * exposure, one_over_gamma)); }
@@ -63,7 +64,6 @@ struct ToColor {
     const float gamma = 2.2f, level = 1.0f;
     one_over_gamma = 1.0f / gamma;
     exposure = (float)std::sqrt(std::pow(2, level));
-    uint32_t thr[256];
     thr[0] = 0;
     for (uint32_t k = 1; k < 256; ++k) thr[k] = first_reaching(k, thr[k - 1], kInf);
     const uint32_t nb = (kInf >> 15) + 1;
@@ -109,6 +109,12 @@ extern "C" int pt_to_color(const float* hdr, int32_t width, int32_t height, int3
       frame[(size_t)x + (size_t)y * (size_t)width] =
           (255u << 24) + (T.code(s[2]) << 16) + (T.code(s[1]) << 8) + T.code(s[0]);
     }
+  return PT_OK;
+}
+
+extern "C" int pt_to_color_thresholds(uint32_t thr_bits[256]) {
+  if (!thr_bits) return pt_fail(PT_E_INVALID, "pt_to_color_thresholds: NULL argument");
+  std::memcpy(thr_bits, table().thr, sizeof(table().thr));
   return PT_OK;
 }
 

@@ -24,6 +24,7 @@
 
 #include "../../include/ptgpu.h"
 #include "../../include/ptgpu_scene.h"
+#include "film.h"
 #include "pt_device.h"
 #include "pt_error.h"
 
@@ -277,6 +278,31 @@ struct pt_ctx {
   int grid_plain = 0, grid_stats = 0;
   int bpc_plain = 0, bpc_stats = 0, n_cu = 0;
   int bpc_variant[4] = {0, 0, 0, 0};  // plain builds: [env * 2 + gtab] (the common one is bpc_plain)
+  std::vector<pt_film*> films;  // films not yet destroyed (pt_destroy frees them)
+  DevBuf<uint32_t> tc_thr;      // pt_to_color_thresholds on the device (uploaded at first use)
+  bool tc_thr_ready = false;
+};
+
+// A progressive film (ptgpu.h: pt_film_*; kernels and record layout: film.h).
+struct pt_film {
+  pt_ctx* ctx = nullptr;
+  int W = 0, H = 0;
+  DevBuf<uint4> rec;     // 2 * W * H records
+  DevBuf<float> pass;    // the pass being added (W * H * 3, the frame layout)
+  DevBuf<int4> tiles;    // the last pass's clipped tiles
+  std::vector<int4> tiles_host;  // what `tiles` holds
+  DevBuf<int4> etiles;   // pt_film_tile_error: the listed tiles, and their maxima
+  DevBuf<float> emax;
+  DevBuf<float> out_hdr, out_err;  // pt_film_resolve: device side of the host outputs
+  DevBuf<uint32_t> out_rgba;
+  uint64_t next = 0;     // next sample index (<= 2^32)
+  int64_t passes = 0;
+  hipEvent_t ev_acc[2] = {}, ev_res[2] = {};  // around the last accumulate / resolve kernel
+  bool acc_timed = false, res_timed = false;
+  // the film's last operation: a later one on another stream waits for it
+  hipEvent_t ev_order = nullptr;
+  hipStream_t last_stream = nullptr;
+  bool ordered = false;  // ev_order has been recorded
 };
 
 extern "C" {
@@ -330,11 +356,15 @@ int pt_create(int device, pt_ctx** out) {
 }
 
 static void tile_worker_stop(pt_ctx* c);
+static void film_free(pt_film* f);
 
 int pt_destroy(pt_ctx* c) {
   if (!c) return PT_OK;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();  // no render of this context may still be running
+  for (pt_film* f : c->films) film_free(f);
+  c->films.clear();
+  c->tc_thr.release();
   c->nodes.release();
   c->nodes2.release();
   c->prim_map.release();
@@ -1655,6 +1685,305 @@ int pt_render_tiles_device(pt_ctx* c, const pt_tile* tiles, int32_t n_tiles, flo
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   if ((rc = launch(c, tl, &hdr_out_dev, 1, nullptr, s, flags))) return rc;
   return finish_stats(c, s, flags, false);
+}
+
+// ---- progressive film (ptgpu.h: pt_film_*; kernels and record layout: film.hip, film.h)
+#define FILM_ALLOC(expr)                                                                        \
+  do {                                                                                          \
+    hipError_t _e = (expr);                                                                     \
+    if (_e != hipSuccess) {                                                                     \
+      (void)hipGetLastError();                                                                  \
+      return fail(_e == hipErrorOutOfMemory ? PT_E_ALLOC : PT_E_HIP, std::string(#expr ": ") + hipGetErrorString(_e)); \
+    }                                                                                           \
+  } while (0)
+
+static void film_free(pt_film* f) {
+  f->rec.release();
+  f->pass.release();
+  f->tiles.release();
+  f->etiles.release();
+  f->emax.release();
+  f->out_hdr.release();
+  f->out_err.release();
+  f->out_rgba.release();
+  for (hipEvent_t e : {f->ev_acc[0], f->ev_acc[1], f->ev_res[0], f->ev_res[1], f->ev_order})
+    if (e) (void)hipEventDestroy(e);
+  delete f;
+}
+
+// The toColor thresholds on the device (once per context; a blocking copy, so
+// every kernel queued afterwards sees them).
+static int tonemap_table(pt_ctx* c) {
+  if (c->tc_thr_ready) return PT_OK;
+  uint32_t thr[256];
+  if (int rc = pt_to_color_thresholds(thr)) return rc;
+  FILM_ALLOC(c->tc_thr.reserve(256));
+  HIPCHK(hipMemcpy(c->tc_thr.p, thr, sizeof(thr), hipMemcpyHostToDevice));
+  c->tc_thr_ready = true;
+  return PT_OK;
+}
+
+// Consecutive operations on one film are ordered: one that comes on another
+// stream than the last waits for the last one's event.
+static int film_begin(pt_film* f, hipStream_t s) {
+  if (f->ordered && f->last_stream != s) HIPCHK(hipStreamWaitEvent(s, f->ev_order, 0));
+  return PT_OK;
+}
+static int film_end(pt_film* f, hipStream_t s) {
+  HIPCHK(hipEventRecord(f->ev_order, s));
+  f->last_stream = s;
+  f->ordered = true;
+  return PT_OK;
+}
+
+// True when no two of the non-empty rectangles r = (x0, y0, x1, y1) share a
+// pixel.  Sorted by y0, each is compared with those that begin below its last
+// row only -- for a grid of tiles its own row -- instead of marking W * H bytes
+// (tiles_disjoint) on every pass.
+static bool rects_disjoint(std::vector<int4>& r) {
+  std::sort(r.begin(), r.end(), [](const int4& a, const int4& b) { return a.y != b.y ? a.y < b.y : a.x < b.x; });
+  for (size_t i = 0; i < r.size(); ++i)
+    for (size_t j = i + 1; j < r.size() && r[j].y < r[i].w; ++j)
+      if (r[j].x < r[i].z && r[i].x < r[j].z) return false;
+  return true;
+}
+
+int pt_film_create(pt_ctx* c, int32_t width, int32_t height, pt_film** out) {
+  if (out) *out = nullptr;
+  if (!c || !out) return fail(PT_E_INVALID, "pt_film_create: NULL argument");
+  if (width < 1 || height < 1 || width > 65535 || height > 65535 || (int64_t)width * height > (int64_t)1 << 30)
+    return fail(PT_E_INVALID, "pt_film_create: width and height must be 1 .. 65535 and width * height <= 2^30");
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = tonemap_table(c)) return rc;
+  pt_film* f = new pt_film();
+  f->ctx = c;
+  f->W = width;
+  f->H = height;
+  const size_t px = (size_t)width * (size_t)height;
+  int rc = [&]() -> int {
+    FILM_ALLOC(f->rec.reserve(2 * px));
+    FILM_ALLOC(f->pass.reserve(3 * px));
+    for (hipEvent_t* e : {&f->ev_acc[0], &f->ev_acc[1], &f->ev_res[0], &f->ev_res[1]}) HIPCHK(hipEventCreate(e));
+    HIPCHK(hipEventCreateWithFlags(&f->ev_order, hipEventDisableTiming));
+    HIPCHK(hipMemsetAsync(f->rec.p, 0, 2 * px * sizeof(uint4), c->stream));
+    return film_end(f, c->stream);
+  }();
+  if (rc) {
+    film_free(f);
+    return rc;
+  }
+  c->films.push_back(f);
+  *out = f;
+  return PT_OK;
+}
+
+int pt_film_destroy(pt_film* f) {
+  if (!f) return PT_OK;
+  pt_ctx* c = f->ctx;
+  (void)hipSetDevice(c->device);
+  (void)hipDeviceSynchronize();  // no kernel may still use the film's memory
+  c->films.erase(std::remove(c->films.begin(), c->films.end(), f), c->films.end());
+  film_free(f);
+  return PT_OK;
+}
+
+int pt_film_clear(pt_film* f, void* stream) {
+  if (!f) return fail(PT_E_INVALID, "pt_film_clear: NULL film");
+  pt_ctx* c = f->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (int rc = film_begin(f, s)) return rc;
+  HIPCHK(hipMemsetAsync(f->rec.p, 0, 2 * (size_t)f->W * (size_t)f->H * sizeof(uint4), s));
+  f->next = 0;
+  f->passes = 0;
+  return film_end(f, s);
+}
+
+int pt_film_set_next_sample(pt_film* f, uint32_t next_sample) {
+  if (!f) return fail(PT_E_INVALID, "pt_film_set_next_sample: NULL film");
+  f->next = next_sample;
+  return PT_OK;
+}
+
+int pt_film_add_pass(pt_film* f, const pt_tile* tiles, int32_t n_tiles, void* stream) {
+  if (!f) return fail(PT_E_INVALID, "pt_film_add_pass: NULL film");
+  pt_ctx* c = f->ctx;
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (n_tiles < 0 || (n_tiles > 0 && !tiles)) return fail(PT_E_INVALID, "pt_film_add_pass: bad args");
+  const pt_params& P = c->params;
+  if (P.width != f->W || P.height != f->H)
+    return fail(PT_E_INVALID, "pt_film_add_pass: pt_params frame " + std::to_string(P.width) + " x " +
+                                  std::to_string(P.height) + " differs from the film's " + std::to_string(f->W) + " x " +
+                                  std::to_string(f->H));
+  if (f->next + (uint64_t)P.spp > (uint64_t)1 << 32)
+    return fail(PT_E_INVALID, "pt_film_add_pass: sample range overflow (next sample " + std::to_string(f->next) +
+                                  " + spp " + std::to_string(P.spp) + " > 2^32)");
+  std::vector<int4> rects;
+  for (int32_t i = 0; i < n_tiles; ++i) {
+    const pt_tile& t = tiles[i];
+    if (t.w < 0 || t.h < 0) return fail(PT_E_INVALID, "pt_film_add_pass: negative tile size");
+    const int x0 = std::max(0, t.x), y0 = std::max(0, t.y);
+    const int x1 = (int)std::min<int64_t>(f->W, (int64_t)t.x + t.w), y1 = (int)std::min<int64_t>(f->H, (int64_t)t.y + t.h);
+    if (x1 > x0 && y1 > y0) rects.push_back(make_int4(x0, y0, x1, y1));
+  }
+  if (!rects_disjoint(rects))
+    return fail(PT_E_INVALID, "pt_film_add_pass: tiles overlap (their samples would be counted twice)");
+  if ((rc = tile_launch(c))) return rc;  // earlier asynchronous tiles first (call order)
+  HIPCHK(hipSetDevice(c->device));
+  // the same <= 32x32 pieces the render resolves (build_tiles of the clipped rectangles)
+  std::vector<int4> tl;
+  for (const int4& r : rects)
+    for (int y = r.y; y < r.w; y += 32)
+      for (int x = r.x; x < r.z; x += 32) tl.push_back(make_int4(x, y, std::min(32, r.z - x), std::min(32, r.w - y)));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if ((rc = film_begin(f, s))) return rc;
+  // the pass: the context's params with the film's sample index, through the
+  // render path every other entry point uses; the stored params stay the caller's
+  const uint32_t base = c->params.sample_base;
+  c->params.sample_base = (uint32_t)f->next;
+  float* pass = f->pass.p;
+  rc = launch(c, tl, &pass, 1, nullptr, s, 0);
+  c->params.sample_base = base;
+  if (rc) return rc;
+  if ((rc = finish_stats(c, s, 0, false))) return rc;
+  if (!tl.empty()) {
+    if (tl.size() != f->tiles_host.size() || std::memcmp(tl.data(), f->tiles_host.data(), tl.size() * sizeof(int4)) != 0) {
+      f->tiles_host.clear();  // (not what the device holds, should the upload fail)
+      FILM_ALLOC(f->tiles.reserve(tl.size()));
+      f->tiles_host = tl;  // (the copy's source outlives the call)
+      const hipError_t e = hipMemcpyAsync(f->tiles.p, f->tiles_host.data(), tl.size() * sizeof(int4), hipMemcpyHostToDevice, s);
+      if (e != hipSuccess) f->tiles_host.clear();
+      HIPCHK(e);
+    }
+    FilmAccArgs a;
+    a.tiles = f->tiles.p;
+    a.rec = f->rec.p;
+    a.pass = f->pass.p;
+    a.W = f->W;
+    a.H = f->H;
+    a.spp = (uint32_t)P.spp;
+    HIPCHK(hipEventRecord(f->ev_acc[0], s));
+    HIPCHK(ptk_film_accumulate(&a, (int)tl.size(), s));
+    HIPCHK(hipEventRecord(f->ev_acc[1], s));
+    f->acc_timed = true;
+  }
+  f->next += (uint64_t)P.spp;
+  ++f->passes;
+  return film_end(f, s);
+}
+
+int pt_film_resolve_device(pt_film* f, float* hdr_dev, uint32_t* rgba_dev, float* err_dev, void* stream) {
+  if (!f) return fail(PT_E_INVALID, "pt_film_resolve_device: NULL film");
+  if (!hdr_dev && !rgba_dev && !err_dev) return PT_OK;
+  pt_ctx* c = f->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (int rc = film_begin(f, s)) return rc;
+  FilmResolveArgs a;
+  a.rec = f->rec.p;
+  a.thr = c->tc_thr.p;
+  a.hdr = hdr_dev;
+  a.rgba = rgba_dev;
+  a.err = err_dev;
+  a.W = f->W;
+  a.H = f->H;
+  HIPCHK(hipEventRecord(f->ev_res[0], s));
+  HIPCHK(ptk_film_resolve(&a, s));
+  HIPCHK(hipEventRecord(f->ev_res[1], s));
+  f->res_timed = true;
+  return film_end(f, s);
+}
+
+int pt_film_resolve(pt_film* f, float* hdr_host, uint32_t* rgba_host, float* err_host) {
+  if (!f) return fail(PT_E_INVALID, "pt_film_resolve: NULL film");
+  pt_ctx* c = f->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t px = (size_t)f->W * (size_t)f->H;
+  if (hdr_host) FILM_ALLOC(f->out_hdr.reserve(3 * px));
+  if (rgba_host) FILM_ALLOC(f->out_rgba.reserve(px));
+  if (err_host) FILM_ALLOC(f->out_err.reserve(px));
+  if (int rc = pt_film_resolve_device(f, hdr_host ? f->out_hdr.p : nullptr, rgba_host ? f->out_rgba.p : nullptr,
+                                      err_host ? f->out_err.p : nullptr, nullptr))
+    return rc;
+  hipStream_t s = c->stream;
+  if (hdr_host) HIPCHK(hipMemcpyAsync(hdr_host, f->out_hdr.p, 3 * px * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (rgba_host) HIPCHK(hipMemcpyAsync(rgba_host, f->out_rgba.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  if (err_host) HIPCHK(hipMemcpyAsync(err_host, f->out_err.p, px * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return PT_OK;
+}
+
+int pt_film_tile_error(pt_film* f, const pt_tile* tiles, int32_t n_tiles, float* err_host) {
+  if (!f) return fail(PT_E_INVALID, "pt_film_tile_error: NULL film");
+  if (n_tiles < 0 || (n_tiles > 0 && (!tiles || !err_host))) return fail(PT_E_INVALID, "pt_film_tile_error: bad args");
+  if (n_tiles == 0) return PT_OK;
+  std::vector<int4> tl((size_t)n_tiles);
+  for (int32_t i = 0; i < n_tiles; ++i) {
+    const pt_tile& t = tiles[i];
+    if (t.w < 0 || t.h < 0) return fail(PT_E_INVALID, "pt_film_tile_error: negative tile size");
+    const int x0 = std::max(0, t.x), y0 = std::max(0, t.y);
+    const int x1 = (int)std::min<int64_t>(f->W, (int64_t)t.x + t.w), y1 = (int)std::min<int64_t>(f->H, (int64_t)t.y + t.h);
+    tl[i] = x1 > x0 && y1 > y0 ? make_int4(x0, y0, x1 - x0, y1 - y0) : make_int4(0, 0, 0, 0);
+  }
+  pt_ctx* c = f->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  FILM_ALLOC(f->etiles.reserve(tl.size()));
+  FILM_ALLOC(f->emax.reserve(tl.size()));
+  hipStream_t s = c->stream;
+  if (int rc = film_begin(f, s)) return rc;
+  HIPCHK(hipMemcpyAsync(f->etiles.p, tl.data(), tl.size() * sizeof(int4), hipMemcpyHostToDevice, s));
+  FilmErrArgs a;
+  a.tiles = f->etiles.p;
+  a.rec = f->rec.p;
+  a.out = f->emax.p;
+  a.W = f->W;
+  a.H = f->H;
+  HIPCHK(ptk_film_tile_error(&a, n_tiles, s));
+  HIPCHK(hipMemcpyAsync(err_host, f->emax.p, tl.size() * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (int rc = film_end(f, s)) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  return PT_OK;
+}
+
+int pt_film_get_info(pt_film* f, pt_film_info* out) {
+  if (!f || !out) return fail(PT_E_INVALID, "pt_film_get_info: NULL argument");
+  std::memset(out, 0, sizeof(*out));
+  out->width = f->W;
+  out->height = f->H;
+  out->passes = f->passes;
+  out->next_sample = f->next;
+  float ms = 0.f;
+  if (f->acc_timed) {
+    HIPCHK(hipEventSynchronize(f->ev_acc[1]));
+    HIPCHK(hipEventElapsedTime(&ms, f->ev_acc[0], f->ev_acc[1]));
+    out->accumulate_ms = ms;
+  }
+  if (f->res_timed) {
+    HIPCHK(hipEventSynchronize(f->ev_res[1]));
+    HIPCHK(hipEventElapsedTime(&ms, f->ev_res[0], f->ev_res[1]));
+    out->resolve_ms = ms;
+  }
+  return PT_OK;
+}
+
+int pt_to_color_device(pt_ctx* c, const float* hdr_dev, int32_t width, int32_t height, int32_t x0, int32_t y0,
+                       int32_t x1, int32_t y1, uint32_t* rgba_dev, void* stream) {
+  if (!c || !hdr_dev || !rgba_dev || width < 0 || height < 0) return fail(PT_E_INVALID, "pt_to_color_device: bad args");
+  ToColorArgs a;
+  a.x0 = std::max(0, x0);
+  a.y0 = std::max(0, y0);
+  a.x1 = std::min(width, x1);
+  a.y1 = std::min(height, y1);
+  if (a.x1 <= a.x0 || a.y1 <= a.y0) return PT_OK;
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = tonemap_table(c)) return rc;
+  a.hdr = hdr_dev;
+  a.thr = c->tc_thr.p;
+  a.rgba = rgba_dev;
+  a.W = width;
+  HIPCHK(ptk_to_color(&a, stream ? (hipStream_t)stream : c->stream));
+  return PT_OK;
 }
 
 // Frames of the tile set `tl` one launch of a frame batch takes.  A frame

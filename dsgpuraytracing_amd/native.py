@@ -99,6 +99,13 @@ class pt_stats(ctypes.Structure):
                 ("frames_per_launch", c_int32), ("tile_zorder", c_int32)]
 
 
+class pt_film_info(ctypes.Structure):
+    _fields_ = [("width", c_int32), ("height", c_int32), ("passes", c_int64), ("next_sample", ctypes.c_uint64),
+                ("accumulate_ms", c_double), ("resolve_ms", c_double)]
+
+
+PT_FILM_LUM_FLOOR = 1e-3  # floor of the film's relative error (include/ptgpu.h), as a float32 in the arithmetic
+
 # Every symbol include/ptgpu.h and include/ptgpu_scene.h declare, with ctypes signatures.
 _SIGS = {
     "pt_create": (c_int32, [c_int32, POINTER(c_void_p)]),
@@ -121,6 +128,18 @@ _SIGS = {
     "pt_last_error": (c_char_p, []),
     "pt_to_color": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "pt_to_color_check": (c_int64, [c_uint32, c_uint32]),
+    "pt_to_color_thresholds": (c_int32, [c_void_p]),
+    "pt_to_color_device": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                     c_void_p]),
+    "pt_film_create": (c_int32, [c_void_p, c_int32, c_int32, POINTER(c_void_p)]),
+    "pt_film_destroy": (c_int32, [c_void_p]),
+    "pt_film_clear": (c_int32, [c_void_p, c_void_p]),
+    "pt_film_add_pass": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p]),
+    "pt_film_resolve_device": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pt_film_resolve": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pt_film_tile_error": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p]),
+    "pt_film_get_info": (c_int32, [c_void_p, POINTER(pt_film_info)]),
+    "pt_film_set_next_sample": (c_int32, [c_void_p, c_uint32]),
     "pt_env_search_check": (c_int64, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
     # include/ptgpu_scene.h (bound with full types in scene_loader.py)
     "pt_host_scene_load": (c_int32, [c_char_p, c_int32, c_int32, c_char_p, POINTER(c_void_p)]),

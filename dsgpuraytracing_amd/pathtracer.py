@@ -51,8 +51,11 @@ class Device:
         self.handle = h
         self.device = device
         self._scene_keepalive = None
+        self._films: List["Film"] = []
 
     def close(self):
+        for f in list(getattr(self, "_films", [])):  # (pt_destroy would free them: their handles die with it)
+            f.close()
         if self.handle:
             self._lib.pt_destroy(self.handle)
             self.handle = None
@@ -203,6 +206,11 @@ class Device:
         check(self._lib.pt_get_launch_times(self.handle, k.ctypes.data, r.ctypes.data, n, ctypes.byref(got)))
         return k[:got.value].copy(), r[:got.value].copy()
 
+    def film(self, width: int, height: int) -> "Film":
+        """A progressive film of this context (pt_film_create): device memory
+        that accumulates passes and resolves on the GPU."""
+        return Film(self, width, height)
+
     def wave_trace(self) -> np.ndarray:
         """Per-wave records of the last stats launch (pt_get_wave_trace):
         int64 (waves, 11) = start, first empty-queue time (-1: never), end,
@@ -215,6 +223,88 @@ class Device:
         buf = np.zeros((n.value, 11), np.int64)
         check(self._lib.pt_get_wave_trace(self.handle, buf.ctypes.data, buf.size, ctypes.byref(n)))
         return buf
+
+
+class Film:
+    """One pt_film: the device-resident running result of progressive passes
+    (include/ptgpu.h: the per-pixel arithmetic, stream semantics and errors)."""
+
+    def __init__(self, dev: Device, width: int, height: int):
+        self._lib = dev._lib
+        self._dev = dev
+        self.handle = None
+        h = ctypes.c_void_p()
+        check(self._lib.pt_film_create(dev.handle, int(width), int(height), ctypes.byref(h)))
+        self.handle = h
+        self.width, self.height = int(width), int(height)
+        dev._films.append(self)
+
+    def close(self):
+        if self.handle:
+            self._lib.pt_film_destroy(self.handle)
+            self.handle = None
+            if self in self._dev._films:
+                self._dev._films.remove(self)
+
+    def __del__(self):  # pragma: no cover - interpreter teardown order
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self, stream: int = 0):
+        check(self._lib.pt_film_clear(self.handle, ctypes.c_void_p(stream or None)))
+
+    def add_pass(self, tiles, stream: int = 0):
+        """Render `tiles` with the context's params at the film's next sample
+        index and accumulate them (pt_film_add_pass); returns once queued."""
+        keep, arr = Device._tiles(tiles)
+        check(self._lib.pt_film_add_pass(self.handle, arr, len(keep), ctypes.c_void_p(stream or None)))
+
+    def resolve(self, hdr: bool = True, rgba: bool = True, err: bool = True):
+        """(hdr (H, W, 3) float32, rgba (H, W, 4) uint8, err (H, W) float32) of
+        the whole frame (pt_film_resolve; waits).  An output switched off is
+        None and is neither computed nor copied."""
+        h, w = self.height, self.width
+        o_hdr = np.empty((h, w, 3), np.float32) if hdr else None
+        o_rgba = np.empty((h, w), np.uint32) if rgba else None
+        o_err = np.empty((h, w), np.float32) if err else None
+        check(self._lib.pt_film_resolve(self.handle, *[None if a is None else a.ctypes.data
+                                                       for a in (o_hdr, o_rgba, o_err)]))
+        return o_hdr, None if o_rgba is None else o_rgba.view(np.uint8).reshape(h, w, 4), o_err
+
+    def resolve_device(self, hdr_ptr: int = 0, rgba_ptr: int = 0, err_ptr: int = 0, stream: int = 0):
+        """pt_film_resolve_device: device pointers (0 = not wanted) of W*H*3
+        float32, W*H uint32 and W*H float32; queued on `stream`."""
+        check(self._lib.pt_film_resolve_device(self.handle, ctypes.c_void_p(hdr_ptr or None),
+                                               ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(err_ptr or None),
+                                               ctypes.c_void_p(stream or None)))
+
+    def tile_error(self, tiles) -> np.ndarray:
+        """Per listed tile (clipped to the frame) the maximum of the error over
+        its pixels: +inf while a pixel has fewer than two passes (waits)."""
+        keep, arr = Device._tiles(tiles)
+        out = np.zeros(len(keep), np.float32)
+        check(self._lib.pt_film_tile_error(self.handle, arr, len(keep), out.ctypes.data))
+        return out
+
+    def set_next_sample(self, next_sample: int):
+        """The sample index the next pass starts at (pt_film_set_next_sample)."""
+        check(self._lib.pt_film_set_next_sample(self.handle, int(next_sample)))
+
+    def info(self) -> dict:
+        i = native.pt_film_info()
+        check(self._lib.pt_film_get_info(self.handle, ctypes.byref(i)))
+        return {k: getattr(i, k) for k, _ in native.pt_film_info._fields_}
+
+
+def to_color_device(dev: Device, hdr_ptr: int, w: int, h: int, rgba_ptr: int, rect=None, stream: int = 0):
+    """pt_to_color_device: to_color of the device buffer at hdr_ptr ((h, w, 3)
+    float32) into rgba_ptr ((h, w) uint32) for rect = (x0, y0, x1, y1), the
+    whole frame by default; queued on `stream`."""
+    x0, y0, x1, y1 = (0, 0, w, h) if rect is None else (int(v) for v in rect)
+    check(dev._lib.pt_to_color_device(dev.handle, ctypes.c_void_p(hdr_ptr or None), int(w), int(h), x0, y0, x1, y1,
+                                      ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(stream or None)))
 
 
 class Scene:
@@ -302,6 +392,7 @@ class PathTracer:
         self.gpu_bvh = bool(gpu_bvh)  # build the BVH on the GPU (PARALLEL_BUILD_BVH, setup.cu:188-189)
         self._dev: Optional[Device] = None
         self.last_stats: dict = {}
+        self.last_progressive: dict = {}  # render_progressive: tiles, passes per tile, final tile errors
 
     # ---- configuration (pathtracer.cpp:76-127)
     def _device(self) -> Device:
@@ -438,6 +529,44 @@ class PathTracer:
         h, w = self.sampleBuffer.shape[:2]
         self.render_tiles(tile_fifo(w, h), stats=stats)
         self.state = State.DONE
+
+    def render_progressive(self, passes: int, target_error: Optional[float] = None):
+        """Progressive rendering on a device film: up to `passes` passes of
+        ns_aa fresh samples each over the tiles still active, accumulated on
+        the GPU.  With a target, after every pass from the second on a tile
+        whose error (Film.tile_error: the largest relative standard error of
+        its pixels' mean luminance) is <= target_error leaves the active set;
+        it stops when the set is empty.  sampleBuffer / frameBuffer come from
+        the film's resolve; self.last_progressive records the tiles, the
+        passes each one received and its final error."""
+        if not self.has_valid_configuration():
+            raise RuntimeError("PathTracer is not configured (scene, camera, frame size)")
+        h, w = self.sampleBuffer.shape[:2]
+        self._params()
+        dev = self._device()
+        tiles = tile_fifo(w, h)
+        counts = np.zeros(len(tiles), np.int64)
+        active = list(range(len(tiles)))
+        film = dev.film(w, h)
+        try:
+            for p in range(int(passes)):
+                if not active:
+                    break
+                film.add_pass([tiles[i] for i in active])
+                counts[active] += 1
+                if target_error is not None and p >= 1:
+                    e = film.tile_error([tiles[i] for i in active])
+                    active = [i for i, v in zip(active, e) if not v <= target_error]
+            hdr, rgba, _ = film.resolve(err=False)
+            errors = film.tile_error(tiles)
+            info = film.info()
+        finally:
+            film.close()
+        self.sampleBuffer[...] = hdr
+        self.frameBuffer[...] = rgba
+        self.last_stats = dev.stats()
+        self.last_progressive = {"tiles": tiles, "passes": counts, "tile_error": errors,
+                                 "spp": self.ns_aa, "total_passes": int(info["passes"])}
 
     def stop(self):
         if self.state in (State.RENDERING, State.DONE):

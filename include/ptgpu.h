@@ -41,6 +41,10 @@
  *                               (src/bvh.cpp:331-362) as a batched query
  *   pt_get_stats                timers/counters (pathtracer.cpp:615-632, setup.cu:546-685)
  *   pt_last_error               replaces fprintf+exit(EXIT_FAILURE) (setup.cu:139-143, ...)
+ *   pt_to_color_device          HDRImageBuffer::toColor (src/image.h:174-189) on the device
+ *   pt_film_*                   no counterpart: a device-resident progressive film (accumulated
+ *                               passes, per-pixel error, GPU resolve to HDR / RGBA8 / error) for
+ *                               the display loop that redraws frameBuffer (application.cpp:142-160)
  *
  * Conventions: plain C types and host pointers only; the caller owns every host
  * input and output; the library owns device memory until pt_destroy.  Calls on
@@ -342,6 +346,98 @@ const char* pt_last_error(void);
  * 255).  Pixels outside [x0,x1) x [y0,y1) are left untouched. */
 int pt_to_color(const float* hdr, int32_t width, int32_t height, int32_t x0, int32_t y0, int32_t x1, int32_t y1,
                 uint32_t* frame);
+/* The 255 steps of pt_to_color's channel code (host only, no device): a channel's
+ * 8-bit code is a non-decreasing step function of the float's bit pattern, and
+ * thr_bits[k], k = 1..255, is the smallest non-negative float's bits whose code
+ * reaches k, found with the reference arithmetic itself; thr_bits[0] = 0.  So
+ * code(s) = #{k >= 1 : bits(s) >= thr_bits[k]} for every s without the sign
+ * bit (a positive NaN: 255); with it, -0.0f gives 0 and everything else 255.
+ * This is the whole table the device tonemap (pt_to_color_device, the film's
+ * resolve) searches. */
+int pt_to_color_thresholds(uint32_t thr_bits[256]);
+/* pt_to_color on the device: the RGBA8 codes of the device HDR buffer hdr_dev
+ * (width*height*3 float) into rgba_dev (width*height uint32) for the pixels
+ * of [x0,x1) x [y0,y1), clamped to the frame as pt_to_color clamps it; the
+ * rest is left untouched.  Equal to pt_to_color bit for bit, for every float
+ * (pt_to_color stays the definition).  Queued on `stream` (NULL = the
+ * context's stream) as pt_render_tiles_device queues its work; returns
+ * without waiting. */
+int pt_to_color_device(pt_ctx* ctx, const float* hdr_dev, int32_t width, int32_t height, int32_t x0, int32_t y0,
+                       int32_t x1, int32_t y1, uint32_t* rgba_dev, void* stream);
+
+/* ---- Progressive film (no reference counterpart: the reference renders one
+ * pass and forgets it; its display loop, Application::render ->
+ * PathTracer::update_screen, application.cpp:142-160, pathtracer.cpp:129-148,
+ * redraws frameBuffer).  A film is device memory of one frame size owned by a
+ * context: it accumulates passes, keeps a per-pixel error estimate, and
+ * resolves on the GPU to the HDR mean, to pt_to_color's RGBA8 codes and to
+ * the error, so a display loop copies 4 B per pixel instead of 12 and
+ * tonemaps nothing on the host, and a caller can drop converged tiles.
+ *
+ * Per-pixel state: sum[3] f32, n u32, mu f32, M2 f32, k u32, all zero when
+ * clear.  For a pixel inside a pass's tiles whose pass value is m -- exactly
+ * what pt_render_tiles_device writes for the context's params with
+ * sample_base = the film's next sample index -- and w = (float)spp, each line
+ * one separately rounded IEEE f32 operation per operator, nothing fused:
+ *   sum_c = sum_c + m_c * w                              c = r, g, b
+ *   n     = n + spp
+ *   L     = (0.2126f*m_r + 0.7152f*m_g) + 0.0722f*m_b    (Spectrum::illum)
+ *   W     = (float)n
+ *   d     = L - mu
+ *   mu    = mu + d * (w / W)
+ *   M2    = M2 + (w * d) * (L - mu)
+ *   k     = k + 1
+ * Resolve: hdr_c = n ? sum_c / (float)n : 0;  rgba = pt_to_color(hdr)
+ * (0xFF000000 for a pixel never rendered);
+ *   err = k < 2 ? +inf
+ *               : sqrtf((fmaxf(M2, 0) / (float)n) / (float)(k - 1)) / fmaxf(mu, PT_FILM_LUM_FLOOR)
+ * the standard error of the pass-weighted mean luminance relative to that
+ * mean (floored).
+ *
+ * Calls on a context and its films are serialised by the caller.  Stream
+ * semantics are pt_render_tiles_device's: a call returns when its work is
+ * queued, results are written in `stream` order (NULL = the context's
+ * stream); when consecutive operations on one film come on different streams
+ * the library orders them with an event.  pt_destroy frees a context's
+ * remaining films (their handles are dead afterwards). */
+#define PT_FILM_LUM_FLOOR 1e-3f
+typedef struct pt_film pt_film;
+typedef struct pt_film_info {
+  int32_t width;
+  int32_t height;
+  int64_t passes;        /* pt_film_add_pass calls since creation / the last pt_film_clear */
+  uint64_t next_sample;  /* sample index the next pass starts at (0 .. 2^32) */
+  double accumulate_ms;  /* device time of the last accumulate kernel (hipEvent; 0: none yet) */
+  double resolve_ms;     /* device time of the last resolve kernel (hipEvent; 0: none yet) */
+} pt_film_info;
+int pt_film_create(pt_ctx* ctx, int32_t width, int32_t height, pt_film** out);
+int pt_film_destroy(pt_film* film); /* NULL is PT_OK */
+/* As freshly created: every record zero, the next sample index back to 0. */
+int pt_film_clear(pt_film* film, void* stream);
+/* Renders the listed tiles with the context's scene, camera and pt_params --
+ * except sample_base, for which the film substitutes its next sample index --
+ * into a pass buffer the film owns, and accumulates them.  The index then
+ * advances by spp whatever the tile list, so K passes of s samples draw
+ * exactly the sample set of one K*s-sample render.  The context's params are
+ * unchanged afterwards.  PT_E_INVALID (film unchanged): the params' frame
+ * size differs from the film's, tiles of one call overlap (a sample set would
+ * count twice), or next_sample + spp > 2^32. */
+int pt_film_add_pass(pt_film* film, const pt_tile* tiles, int32_t n_tiles, void* stream);
+/* Whole-frame resolve into device buffers, each nullable, laid out as the
+ * frame: hdr W*H*3 float (y = 0 at the bottom), rgba W*H uint32 as pt_to_color
+ * writes it, err W*H float. */
+int pt_film_resolve_device(pt_film* film, float* hdr_dev, uint32_t* rgba_dev, float* err_dev, void* stream);
+/* The same into host buffers; waits.  A display loop passes only rgba_host. */
+int pt_film_resolve(pt_film* film, float* hdr_host, uint32_t* rgba_host, float* err_host);
+/* err_host[i] = the maximum of err over tile i clipped to the frame: +inf while
+ * any of its pixels has fewer than two passes, 0 for an empty clipped tile.  Waits. */
+int pt_film_tile_error(pt_film* film, const pt_tile* tiles, int32_t n_tiles, float* err_host);
+/* Waits for the last accumulate and resolve kernels (their times). */
+int pt_film_get_info(pt_film* film, pt_film_info* out);
+/* Sets the sample index the next pass starts at (a film that continues an
+ * earlier render, or one rank's share of a sample split).  Host state only. */
+int pt_film_set_next_sample(pt_film* film, uint32_t next_sample);
+
 /* Diagnostics for pt_to_color's tabulated codes: the number of float bit patterns in
  * [lo_bits, hi_bits) whose tabulated 8-bit code differs from the direct evaluation
  * code8(powf(s * exposure, 1 / 2.2)) (0 = the table is exact there). */
