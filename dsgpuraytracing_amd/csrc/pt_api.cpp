@@ -15,6 +15,7 @@
 #include <deque>
 #include <mutex>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -25,6 +26,7 @@
 #include "../../include/ptgpu.h"
 #include "../../include/ptgpu_scene.h"
 #include "film.h"
+#include "launch_plan.h"
 #include "pt_device.h"
 #include "pt_error.h"
 
@@ -65,6 +67,19 @@ struct DevBuf {
     n = count;
   }
 };
+
+// A device list with a host mirror of what it holds: uploaded (on `s`) only
+// when it changed -- the lists rarely change between frames.  Never a null
+// device list: an empty one (a launch may cull every block) still has an array.
+template <class D, class T>
+int sync_list(DevBuf<D>& dev, std::vector<T>& mirror, const T* list, size_t n, hipStream_t s) {
+  static_assert(sizeof(D) == sizeof(T), "the list uploads without conversion");
+  HIPCHK(dev.reserve(n));
+  if (n == mirror.size() && std::memcmp(list, mirror.data(), n * sizeof(T)) == 0) return PT_OK;
+  mirror.assign(list, list + n);
+  if (n) HIPCHK(hipMemcpyAsync(dev.p, mirror.data(), n * sizeof(T), hipMemcpyHostToDevice, s));
+  return PT_OK;
+}
 
 float round_down(double x) {
   float f = (float)x;
@@ -205,7 +220,7 @@ struct pt_ctx {
   // Small launches (a strong split's share of a frame: few work slots per
   // resident lane) rotate over all kSlots slots, so up to four frames are in
   // flight; larger ones over the first two (three slots measured C3 -6%, four
-  // -10%: profiles/r6/ab_render_slots.txt).  See launch(): small launches.
+  // -10%: profiles/r6/ab_render_slots.txt).  See plan_launch (launch_plan.cpp): small launches.
   static constexpr int kSlots = 4;
   static constexpr int kSlotsLarge = 2;
   uint64_t slot_rr = 0;      // launches issued on the pipeline (slot rotation)
@@ -213,9 +228,9 @@ struct pt_ctx {
   hipStream_t rstream[kSlots] = {};
   hipEvent_t ev_free[kSlots] = {};
   DevBuf<int4> tiles[kSlots];
-  std::vector<int4> tiles_host[kSlots];  // what `tiles` holds
+  std::vector<PlanRect> tiles_host[kSlots];  // what `tiles` holds
   DevBuf<int4> blocks[kSlots];           // footprint-clipped 8x8 pixel blocks of the tiles
-  std::vector<int4> blocks_host[kSlots];
+  std::vector<PlanRect> blocks_host[kSlots];
   DevBuf<int> tblock0[kSlots];           // first block of each tile (+ the end), for the resolve
   std::vector<int> tblock0_host[kSlots];
   DevBuf<int> tout[kSlots];              // caller's index of each launched tile (a Z-ordered packed launch)
@@ -1055,223 +1070,47 @@ static int build_tiles(pt_ctx* c, const pt_tile* tiles, int32_t n, std::vector<i
   return PT_OK;
 }
 
-// Conservative pixel rectangle covering the scene box as seen by the camera.
-// Camera::generate_ray (camera.cpp:113-129) sends every ray of every pixel
-// through the pinhole `pos` with direction c2w * ((fx-.5)W/d, (fy-.5)H/d, -1);
-// a box entirely in front of the pinhole projects inside the rectangle of its
-// 8 projected corners.  Rays start one unit BEHIND the pinhole, so the
-// rectangle is only used when the box lies in front of the pinhole plane;
-// otherwise (false) no pixel can be culled.  One pixel of margin absorbs
-// rounding.  r = (x0, y0, x1, y1), inclusive, NOT clamped to the frame.
-static bool footprint_rect(const pt_ctx* c, int W, int H, int r[4]) {
-  const pt_camera& cam = c->cam;
-  for (int i = 0; i < 3; ++i)  // coordinates by dot products need an orthonormal c2w
-    for (int j = 0; j < 3; ++j) {
-      double dp = 0;
-      for (int k = 0; k < 3; ++k) dp += cam.c2w[3 * k + i] * cam.c2w[3 * k + j];
-      if (std::fabs(dp - (i == j ? 1.0 : 0.0)) > 1e-9) return false;
-    }
-  double ax = cam.screen_w / cam.screen_dist, ay = cam.screen_h / cam.screen_dist;
-  double x0 = 1e300, x1 = -1e300, y0 = 1e300, y1 = -1e300;
-  for (int k = 0; k < 8; ++k) {
-    double X[3] = {(k & 1) ? c->root_hi_d[0] : c->root_lo_d[0], (k & 2) ? c->root_hi_d[1] : c->root_lo_d[1],
-                   (k & 4) ? c->root_hi_d[2] : c->root_lo_d[2]};
-    double v[3] = {X[0] - cam.pos[0], X[1] - cam.pos[1], X[2] - cam.pos[2]};
-    double cx = 0, cy = 0, cz = 0;  // coordinates along the c2w columns
-    for (int i = 0; i < 3; ++i) {
-      cx += v[i] * cam.c2w[3 * i + 0];
-      cy += v[i] * cam.c2w[3 * i + 1];
-      cz += v[i] * cam.c2w[3 * i + 2];
-    }
-    double depth = -cz;  // the view direction is -column 2
-    if (!(depth > 1e-6 * (std::fabs(cx) + std::fabs(cy) + 1.0))) return false;  // behind / at the pinhole plane
-    double fx = 0.5 + cx / depth / ax, fy = 0.5 + cy / depth / ay;
-    x0 = std::min(x0, fx * W);
-    x1 = std::max(x1, fx * W);
-    y0 = std::min(y0, fy * H);
-    y1 = std::max(y1, fy * H);
+// The launch policy's rectangles are the device's int4 (x, y, w, h): tile and
+// block lists go to the device, and tile lists into a plan, without conversion.
+static_assert(sizeof(PlanRect) == sizeof(int4) && offsetof(PlanRect, x) == offsetof(int4, x) &&
+                  offsetof(PlanRect, y) == offsetof(int4, y) && offsetof(PlanRect, w) == offsetof(int4, z) &&
+                  offsetof(PlanRect, h) == offsetof(int4, w),
+              "PlanRect is laid out as int4");
+
+// What the launch policy (launch_plan.h) reads of the context, for `nf` frames of the tiles `tl`.
+static PlanInput plan_input(const pt_ctx* c, const std::vector<int4>& tl, int nf, uint32_t flags, bool gpu_idle,
+                            const LaunchKnobs& knobs) {
+  PlanInput in;
+  in.W = c->params.width;
+  in.H = c->params.height;
+  in.spp = c->params.spp;
+  in.cam = c->cam;
+  for (int k = 0; k < 3; ++k) {
+    in.box_lo[k] = c->root_lo_d[k];
+    in.box_hi[k] = c->root_hi_d[k];
   }
-  // pixel x covers [x, x+1) in fx*W
-  r[0] = (int)std::max(-1.0, std::floor(x0) - 1);
-  r[2] = (int)std::min((double)W, std::floor(x1) + 1);
-  r[1] = (int)std::max(-1.0, std::floor(y0) - 1);
-  r[3] = (int)std::min((double)H, std::floor(y1) + 1);
-  return true;
+  in.env = c->env_w > 0;
+  in.n_bsdfs = c->n_bsdfs;
+  in.n_lights = c->n_lights;
+  in.n_render_nodes = (int64_t)c->n_render_nodes;
+  in.bvh_stack = c->bvh_stack;
+  in.tri_only = c->tri_only;
+  in.n_cu = c->n_cu;
+  in.grid_plain = c->grid_plain;
+  in.grid_stats = c->grid_stats;
+  std::copy(c->bpc_variant, c->bpc_variant + 4, in.bpc_variant);
+  in.stats_cap = c->stats.n;
+  in.tiles = reinterpret_cast<const PlanRect*>(tl.data());
+  in.n_tiles = tl.size();
+  in.nf = nf;
+  in.flags = flags;
+  in.gpu_idle = gpu_idle;
+  in.knobs = knobs;
+  return in;
 }
 
-// The culling rectangle: pixels outside [cull_x0, cull_x1] x [cull_y0,
-// cull_y1] see no geometry (not traced, resolved to 0).
-static void screen_footprint(const pt_ctx* c, KParams& P) {
-  P.cull_x0 = 0;
-  P.cull_y0 = 0;
-  P.cull_x1 = P.W - 1;
-  P.cull_y1 = P.H - 1;
-  if (std::getenv("PT_NO_FOOTPRINT_CULL")) return;
-  if (c->env_w > 0) return;  // rays that miss the scene see the environment map
-  int r[4];
-  if (!footprint_rect(c, P.W, P.H, r)) return;
-  P.cull_x0 = r[0];
-  P.cull_y0 = r[1];
-  P.cull_x1 = r[2];
-  P.cull_y1 = r[3];
-}
-
-// Pixels whose camera rays can reach the scene: the footprint's area inside
-// the frame, or the whole frame with an environment light (misses see the
-// map) or no footprint.  A property of the frame -- PT_NO_FOOTPRINT_CULL
-// leaves it alone -- for the sample-group size.
-static int64_t traced_px(const pt_ctx* c, int W, int H) {
-  int r[4];
-  if (c->env_w > 0 || !footprint_rect(c, W, H, r)) return (int64_t)W * H;
-  const int64_t w = std::min(W - 1, r[2]) - std::max(0, r[0]) + 1, h = std::min(H - 1, r[3]) - std::max(0, r[1]) + 1;
-  return std::max<int64_t>(0, w) * std::max<int64_t>(0, h);
-}
-
-// Sample groups of a pixel (KParams: n_groups groups of group_spp samples,
-// the last one possibly short).  The grouping decides the float summation
-// order of a pixel, so it is a function of the FRAME only -- its size, spp,
-// the pixels its camera rays can reach, the environment light -- never of
-// the launch's tile set, of a stats build or of the device: any split of a
-// frame into tile launches (raytrace_tile calls, the multi-GPU shards) and
-// any device (a CPX partition, fewer resident waves) sums every pixel in the
-// same order.  The slots-per-lane rule below counts the lanes of a whole
-// MI355X at the default occupancy (PT_GROUP_REF_LANES: 256 CUs x 20 waves x
-// 64), not the running device's.
-//  * group_spp: 4 (C4 +4%, framed C3 +2% over 2), 2 with an environment
-//    light (C5 +2.3%, c5big +2.1%), halved until the traced samples make >= 24
-//    work slots per resident lane: C3's footprint-culled frame gets 2 (+1.5%
-//    pipelined, its lone launch 1.70 -> 1.44 ms: half the work in flight when
-//    the queue runs dry), C1 / C2 get 1 (profiles/r4/ab_group_size.txt);
-//  * (a tail of one-sample groups handed out last, to end the launch on short
-//    work slots, measured -2% pipelined for +2% on a lone frame: DESIGN.md §4).
-//  * `budget_waves` bounds the 32-bit slot indices: the largest grid any
-//    launch of the frame may use (plain or stats build), so a frame that fits
-//    one build fits the other.
-static int group_size(int64_t traced, bool env, int spp, int64_t lanes, int64_t frame_blocks, int64_t budget_waves) {
-  int gs = env ? PT_GROUP_SPP_ENV : PT_GROUP_SPP;
-  while (gs > 1 && traced * ((spp + gs - 1) / gs) < lanes * PT_GROUP_MIN_SLOTS) gs /= 2;
-  if (const char* g = std::getenv("PT_SAMPLE_GROUP")) {  // tuning knob
-    int v = std::atoi(g);
-    if (v > 0) gs = v;
-  }
-  gs = std::max(1, std::min(gs, spp));
-  for (;;) {
-    // 32-bit slot indices (they may overshoot by a static and a claimed
-    // chunk per wave) and a group-sum budget of PT_GROUP_SUM_GIB per render
-    // slot, for the whole frame's blocks (so every tile split gets the same
-    // layout)
-    const int64_t slots = frame_blocks * 64 * ((spp + gs - 1) / gs);
-    if ((slots + 2 * budget_waves * PT_CHUNK_MAX < (int64_t)INT32_MAX && slots * PT_SUM_BYTES <= ((int64_t)PT_GROUP_SUM_GIB << 30)) ||
-        gs >= spp)
-      break;
-    gs = std::min(spp, gs * 2);
-  }
-  return gs;
-}
-
-static int frames_that_fit(const pt_ctx* c, const std::vector<int4>& tl, int nf);
-
-// One render: the render kernel on the slot's render stream, then the resolve
-// on the caller's stream `s`, ordered after the render (see pt_ctx: the render
-// pipeline).  (The resolve on the render stream instead measured one frame
-// +0.03 ms: profiles/r5/ab_resolve_reset_stream.txt.)  `nf` > 1: a frame batch
-// (pt_render_frames_device) -- nf frames of these tiles, frame f keyed by
-// seeds[f] into outs[f], in ONE render launch (the MF kernel) and nf resolves;
-// `seeds` null: the parameters' seed.
-static int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs, int nf, const uint32_t* seeds,
-                  hipStream_t s, uint32_t flags) {
-  const bool stats = (flags & (PT_FLAG_STATS | PT_FLAG_REF_COUNTS)) != 0;
-  std::memset(&c->last, 0, sizeof(c->last));
-  c->times_pending = false;
-  if (tl_in.empty()) return PT_OK;
-  // Large launches over trees larger than two XCD L2s render their tiles in
-  // Z-order (the queue bands below then deal each XCD a compact region
-  // rather than a strip of rows: C5 +2.5%, c5big +2.7%; C4's 4-MB tree,
-  // without bands, -0.5% in Z-order, keeps the rows: profiles/r6/
-  // ab_tile_zorder.txt).  Images are per
-  // pixel and sample, identical in any order; packed outputs keep the
-  // caller's tile index (tile_out).  PT_TILE_ZORDER=0/1 forces it (A/B, tests).
-  std::vector<int4> tz;
-  std::vector<int> tperm;
-  {
-    int64_t px = 0;
-    int edge = 1;  // the tile edge: the largest tile's (clipped edge tiles are smaller)
-    for (const int4& t : tl_in) {
-      px += (int64_t)t.z * t.w;
-      edge = std::max(edge, std::max(t.z, t.w));
-    }
-    bool z = tl_in.size() > 1 && px >= ((int64_t)1 << 20) &&
-             (int64_t)c->n_render_nodes * 128 > ((int64_t)PT_BANDS_TREE_MIB << 20);
-    if (const char* zo = std::getenv("PT_TILE_ZORDER")) z = tl_in.size() > 1 && std::atoi(zo) != 0;
-    if (z) {
-      std::vector<uint64_t> key(tl_in.size());
-      for (size_t i = 0; i < tl_in.size(); ++i) {
-        const uint64_t cx = (uint64_t)std::max(0, tl_in[i].x / edge), cy = (uint64_t)std::max(0, tl_in[i].y / edge);
-        uint64_t k = 0;
-        for (int b = 0; b < 21; ++b) k |= ((cx >> b) & 1ull) << (2 * b) | ((cy >> b) & 1ull) << (2 * b + 1);
-        key[i] = k;
-      }
-      tperm.resize(tl_in.size());
-      for (size_t i = 0; i < tperm.size(); ++i) tperm[i] = (int)i;
-      std::stable_sort(tperm.begin(), tperm.end(), [&](int a, int b) { return key[a] < key[b]; });
-      tz.resize(tl_in.size());
-      for (size_t i = 0; i < tz.size(); ++i) tz[i] = tl_in[tperm[i]];
-    }
-  }
-  const std::vector<int4>& tl = tperm.empty() ? tl_in : tz;
-  c->last.tile_zorder = tperm.empty() ? 0 : 1;
-  // PT_PIPELINE=0: every render on the caller's stream, one slot (A/B).  A
-  // census launch (PT_CENSUS) writes its per-wave records into the one shared
-  // trace area, so it never overlaps another launch: it runs unpipelined too.
-  static const bool pipeline = (!std::getenv("PT_PIPELINE") || std::atoi(std::getenv("PT_PIPELINE")) != 0);
-  const bool census_launch = std::getenv("PT_CENSUS") && !stats;
-  const int depth = c->small_last ? pt_ctx::kSlots : pt_ctx::kSlotsLarge;
-  const int slot = pipeline && !census_launch ? (int)(c->slot_rr++ % (uint64_t)depth) : 0;
-  // A launch that finds every slot's last resolve complete has no frame to
-  // overlap with: it runs on the caller's stream, with no cross-stream waits
-  // in front of the render or between the render and the resolve (a lone
-  // frame's wall clock; the slots still alternate).  Only hipErrorNotReady
-  // means busy: any other result is a fault of an earlier render, reported
-  // here instead of being absorbed into the choice (ADVICE r5).
-  bool gpu_idle = true;  // no earlier render of this context still running or queued
-  for (int k = 0; k < pt_ctx::kSlots && gpu_idle; ++k) {
-    if (!c->ev_free[k]) continue;  // (a slot never used)
-    const hipError_t q = hipEventQuery(c->ev_free[k]);
-    if (q == hipErrorNotReady) {
-      (void)hipGetLastError();  // (a not-ready query is no error of this launch)
-      gpu_idle = false;
-    } else if (q != hipSuccess) {
-      return fail(PT_E_HIP, std::string("render: an earlier launch failed: ") + hipGetErrorString(q));
-    }
-  }
-  const bool idle = pipeline && !census_launch && gpu_idle;
-  if (!c->rstream[slot]) {  // a small launch's first use of slots 2 and 3
-    HIPCHK(make_render_stream(&c->rstream[slot]));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_free[slot], hipEventDisableTiming));
-    HIPCHK(hipEventRecord(c->ev_free[slot], c->stream));
-  }
-  hipStream_t rs = pipeline && !census_launch && !idle ? c->rstream[slot] : s;
-  // the slot's device state is free once the previous resolve that read it ran
-  if (!idle) HIPCHK(hipStreamWaitEvent(rs, c->ev_free[slot], 0));
-  // the tile list rarely changes between frames: upload it only when it does
-  std::vector<int4>& th = c->tiles_host[slot];
-  if (tl.size() != th.size() || std::memcmp(tl.data(), th.data(), tl.size() * sizeof(int4)) != 0) {
-    th = tl;
-    HIPCHK(c->tiles[slot].reserve(tl.size()));
-    HIPCHK(hipMemcpyAsync(c->tiles[slot].p, th.data(), th.size() * sizeof(int4), hipMemcpyHostToDevice, rs));
-  }
-  // Queue heads: zeroed by the slot's previous resolve (a memset in front of the render is a dependent launch of its own, ~20 us
-  // before the render kernel starts on a lone frame); a memset only when
-  // that did not happen (first use, a launch that failed half-way)
-  if (!c->counter_clean[slot])
-    HIPCHK(hipMemsetAsync(c->counter[slot].p, 0, PT_QUEUE_WORDS * PT_QUEUE_HEADS * sizeof(uint32_t), rs));
-  c->counter_clean[slot] = false;
-  if (stats) {
-    unsigned long long init[PT_STATS_SLOTS] = {0};
-    init[21] = init[23] = init[25] = ~0ull;  // atomicMin slots
-    HIPCHK(hipMemcpyAsync(c->stats.p, init, sizeof(init), hipMemcpyHostToDevice, rs));
-    HIPCHK(hipStreamSynchronize(rs));  // `init` is a stack array
-  }
+// What the kernels read of the context and of the plan; launch() adds its render slot's buffers.
+static KParams kernel_params(const pt_ctx* c, const LaunchPlan& plan, int nf, const uint32_t* seeds, uint32_t flags) {
   KParams P;
   std::memset(&P, 0, sizeof(P));
   for (int k = 0; k < 3; ++k) {
@@ -1279,6 +1118,8 @@ static int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs,
     P.c2w_col0[k] = (float)c->cam.c2w[3 * k + 0];
     P.c2w_col1[k] = (float)c->cam.c2w[3 * k + 1];
     P.c2w_col2[k] = (float)c->cam.c2w[3 * k + 2];
+    P.root_lo[k] = c->root_lo[k];
+    P.root_hi[k] = c->root_hi[k];
   }
   P.cam_ax = (float)(c->cam.screen_w / c->cam.screen_dist);
   P.cam_ay = (float)(c->cam.screen_h / c->cam.screen_dist);
@@ -1296,7 +1137,6 @@ static int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs,
   for (int f = 0; f < PT_MAX_FRAMES; ++f) P.seeds[f] = seeds && f < nf ? seeds[f] : P.seed;
   P.n_lights = c->n_lights;
   P.n_bsdfs = c->n_bsdfs;
-  P.n_tiles = (int)tl.size();
   P.nodes = c->nodes.p;
   P.nodes2 = c->nodes2.p;
   P.prims = c->prims.p;
@@ -1315,206 +1155,122 @@ static int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs,
   P.env_pdf = c->env_pdf.p;
   P.env_rtheta = c->env_rtheta.p;
   P.env_rphi = c->env_rphi.p;
-  P.tiles = c->tiles[slot].p;
-  P.tile_out = nullptr;
-  if (!tperm.empty() && (flags & (PT_FLAG_PACKED | PT_FLAG_PACKED16))) {
-    std::vector<int>& oh = c->tout_host[slot];
-    if (oh != tperm) {
-      oh = tperm;
-      HIPCHK(c->tout[slot].reserve(oh.size()));
-      HIPCHK(hipMemcpyAsync(c->tout[slot].p, oh.data(), oh.size() * sizeof(int), hipMemcpyHostToDevice, rs));
-    }
-    P.tile_out = c->tout[slot].p;
-  }
-  P.out = outs[0];
   P.packed = (flags & PT_FLAG_PACKED16) ? 16 : (flags & PT_FLAG_PACKED) ? 32 : 0;
-  P.work_counter = c->counter[slot].p;
   P.stats = c->stats.p;
-  P.dbg_pix = -1;
-  for (int k = 0; k < 3; ++k) {
-    P.root_lo[k] = c->root_lo[k];
-    P.root_hi[k] = c->root_hi[k];
-  }
-  screen_footprint(c, P);
-  c->last.footprint[0] = std::max(0, P.cull_x0);
-  c->last.footprint[1] = std::max(0, P.cull_y0);
-  c->last.footprint[2] = std::min(P.W - 1, P.cull_x1);
-  c->last.footprint[3] = std::min(P.H - 1, P.cull_y1);
-  if (c->last.footprint[2] < c->last.footprint[0] || c->last.footprint[3] < c->last.footprint[1]) {
-    c->last.footprint[0] = c->last.footprint[1] = 0;  // nothing visible: the empty rectangle
-    c->last.footprint[2] = c->last.footprint[3] = -1;
-  }
-  P.shade_batch = c->env_w > 0 ? PT_SHADE_BATCH_ENV : PT_SHADE_BATCH;
-  P.leaf_weight = c->env_w > 0 ? PT_LEAF_WEIGHT_ENV : PT_LEAF_WEIGHT;
-  if (const char* lw = std::getenv("PT_LEAF_WEIGHT")) {  // tuning knob
-    int v = std::atoi(lw);
-    if (v >= 1) P.leaf_weight = v;
-  }
-  P.census = census_launch ? 1 : 0;  // diagnostics (tools/wave_trace.py --census)
-  // triangle-only scenes take the render kernel without the sphere test
-  // (branch-free leaf steps); PT_NO_TRI_ONLY forces the mixed one (A/B, tests)
-  P.tri_only = c->tri_only && !std::getenv("PT_NO_TRI_ONLY") ? 1 : 0;
-  // drain helpers; PT_NO_HELPERS turns them off (A/B, tests)
-  P.helpers = std::getenv("PT_NO_HELPERS") ? 0 : 1;
-  P.drain_div = 0;
-  if (const char* dd = std::getenv("PT_DRAIN_DIV")) {  // tuning knob
-    int v = std::atoi(dd);
-    if (v >= 0 && v <= 64) P.drain_div = v;
-  }
-  if (const char* sb = std::getenv("PT_SHADE_BATCH")) {  // tuning knob
-    int v = std::atoi(sb);
-    if (v >= 1 && v <= 64) P.shade_batch = v;
-  }
-  if (const char* dp = std::getenv("PT_DEBUG_PIXEL")) {  // diagnostics only
-    int dx = -1, dy = -1;
-    if (std::sscanf(dp, "%d,%d", &dx, &dy) == 2 && dx >= 0 && dy >= 0 && dx < P.W && dy < P.H) P.dbg_pix = dx + dy * P.W;
-  }
-  // Render blocks: <= 8x8 rectangles of each tile clipped to the footprint,
-  // tile by tile (tb0[i] = the first block of tile i, for the resolve).
-  std::vector<int4> bl;
-  std::vector<int> tb0;
-  tb0.reserve(tl.size() + 1);
-  int64_t px_in = 0, px_all = 0;
-  for (const int4& t : tl) {
-    tb0.push_back((int)bl.size());
-    px_all += (int64_t)t.z * t.w;
-    int x0 = std::max(t.x, P.cull_x0), x1 = std::min(t.x + t.z - 1, P.cull_x1);
-    int y0 = std::max(t.y, P.cull_y0), y1 = std::min(t.y + t.w - 1, P.cull_y1);
-    for (int by = y0; by <= y1; by += 8)
-      for (int bx = x0; bx <= x1; bx += 8) {
-        bl.push_back(make_int4(bx, by, std::min(8, x1 - bx + 1), std::min(8, y1 - by + 1)));
-        px_in += (int64_t)bl.back().z * bl.back().w;
-      }
-  }
-  tb0.push_back((int)bl.size());
-  c->culled_px = px_all - px_in;
-  std::vector<int4>& bh = c->blocks_host[slot];
-  if (!c->blocks[slot].p) HIPCHK(c->blocks[slot].reserve(1));  // never a null block list (a launch may cull every block)
-  if (bl.size() != bh.size() || std::memcmp(bl.data(), bh.data(), bl.size() * sizeof(int4)) != 0) {
-    bh = bl;
-    HIPCHK(c->blocks[slot].reserve(bl.size()));
-    if (!bh.empty())
-      HIPCHK(hipMemcpyAsync(c->blocks[slot].p, bh.data(), bh.size() * sizeof(int4), hipMemcpyHostToDevice, rs));
-  }
-  P.blocks = c->blocks[slot].p;
-  P.n_blocks = (int)bl.size();
-  std::vector<int>& th0 = c->tblock0_host[slot];
-  if (tb0 != th0) {
-    th0 = tb0;
-    HIPCHK(c->tblock0[slot].reserve(tb0.size()));
-    HIPCHK(hipMemcpyAsync(c->tblock0[slot].p, th0.data(), th0.size() * sizeof(int), hipMemcpyHostToDevice, rs));
-  }
-  P.tile_block0 = c->tblock0[slot].p;
-  // Work slots are (pixel, group of group_spp samples): small enough that
-  // the dynamic queue balances the waves (a whole pixel per slot left the
-  // launch waiting on a few waves holding 64-sample pixels).
-  // the launch fills the GPU with the resident waves of the kernel variant it
-  // runs (environment light / global tables; the STATS build for counters)
-  const bool gtab = c->n_bsdfs > PT_LDS_BSDFS || c->n_lights > PT_LDS_LIGHTS || std::getenv("PT_FORCE_GLOBAL_TABLES");
-  int64_t want = stats ? c->grid_stats
-                       : (int64_t)std::max(8, c->bpc_variant[(c->env_w > 0 ? 2 : 0) + (gtab ? 1 : 0)]) * c->n_cu;
-  if (const char* g = std::getenv("PT_WAVES_PER_CU")) {  // tuning knob
-    int w = std::atoi(g);
-    if (w > 0) want = (int64_t)w * c->n_cu;
-  }
-  const int64_t want_plain = std::getenv("PT_WAVES_PER_CU") ? want : c->grid_plain;
-  const int64_t frame_blocks = (int64_t)((P.W + 7) / 8) * ((P.H + 7) / 8);
-  const int64_t budget_waves = std::max({want, want_plain, (int64_t)c->grid_stats});
-  P.group_spp = group_size(traced_px(c, P.W, P.H), c->env_w > 0, P.spp, (int64_t)PT_GROUP_REF_LANES, frame_blocks,
-                           budget_waves);
-  P.n_groups = (P.spp + P.group_spp - 1) / P.group_spp;
-  const int64_t frame_slots = (int64_t)bl.size() * 64 * P.n_groups;
-  const int64_t slots = frame_slots * nf;  // (a frame batch: every frame's slots, frame after frame)
-  P.frame_slots = (uint32_t)frame_slots;
-  pt_fastdiv_init((uint32_t)std::max<int64_t>(frame_slots, 1), &P.frm_m, &P.frm_sh);
-  // (slot indices reach past the end by up to a static chunk plus a claimed one per wave)
-  if (slots + 2 * want * PT_CHUNK_MAX >= (int64_t)INT32_MAX) return fail(PT_E_INVALID, "frame too large for one launch");
-  // Small launches: at most PT_SMALL_SLOTS work slots per lane of the whole
-  // resident grid (a strong split's share of the C3 frame: 12.8 at N = 2,
-  // 3.2 at N = 8; the whole C3 frame has 25.6).  Each lane then renders only
-  // a few slots, so a wave's slowest lane -- not the work -- sets the launch's
-  // time.  They claim 64 slots at a time (one per lane: no wave holds two
-  // while others have none), and when queued behind other frames they run on
-  // half the resident grid with up to kSlots frames in flight (more slots per
-  // lane per launch, the next frames filling each launch's tail).  Measured
-  // on the split's share (one-GPU emulation, profiles/r6/ab_small_launch*.txt):
-  // N = 8 0.38 -> 0.22 ms per frame, N = 4 0.51 -> 0.39, N = 2 0.75 -> 0.66.
-  // Neither the grid nor the claim changes a value (the sample grouping is
-  // a function of the frame).  PT_SMALL_LAUNCH=0 turns it off.
-  static const bool small_on = !std::getenv("PT_SMALL_LAUNCH") || std::atoi(std::getenv("PT_SMALL_LAUNCH")) != 0;
-  const bool small = small_on && pipeline && !census_launch && !stats &&
-                     slots <= (int64_t)PT_SMALL_SLOTS * c->grid_plain * PT_BLOCK;
-  if (!stats) c->small_last = small;
-  if (small && !gpu_idle && !std::getenv("PT_WAVES_PER_CU")) want = std::max<int64_t>(c->n_cu, want / 2);
-  pt_fastdiv_init((uint32_t)P.n_groups, &P.grp_m, &P.grp_sh);
-  // queue claims: bigger for frames with many slots per lane (fewer atomics
-  // on the heads; a lone small frame's drain prefers the smaller claim)
-  // and for a frame queued behind another in the render pipeline
-  // (profiles/r5/ab_chunk_busy.txt): its drain overlaps the previous frame's -- the
-  // throughput case -- while a frame launched on an idle GPU, or with the
-  // pipeline off (PT_PIPELINE=0: no two launches overlap), is the latency
-  // case, whose end the smaller claim shortens
-  // (C3: 256-slot claims +2.9% pipelined, lone launch +9%:
-  // profiles/r5/ab_chunk_heads.txt).  A claim size never changes a value.
-  const bool big_frame = slots >= (int64_t)PT_CHUNK_BIG_SLOTS * want_plain * PT_BLOCK;
-  P.chunk = small ? PT_BLOCK
-          : big_frame || (pipeline && !census_launch && !gpu_idle) ? PT_CHUNK_MAX
-                                                                   : PT_CHUNK;
-  // large frames claim PT_CHUNK_BIG (512) where the slot indices and the
-  // one-block-per-chunk rule allow it: half the atomics again (C5 +1.0%, C4
-  // +0.7%; C3's queued frames lose 7% at 512: profiles/r5/ab_chunk512.txt)
-  if (big_frame && slots + 2 * want * PT_CHUNK_BIG < (int64_t)INT32_MAX && (64 * P.n_groups) % PT_CHUNK_BIG == 0)
-    P.chunk = PT_CHUNK_BIG;
-  if (const char* cs = std::getenv("PT_CHUNK_SLOTS")) {  // tuning knob (64..PT_CHUNK_BIG, a multiple of 64)
-    const int v = std::atoi(cs);
-    if (v >= 64 && v <= PT_CHUNK_BIG && v % 64 == 0 && slots + 2 * want * v < (int64_t)INT32_MAX) P.chunk = v;
-  }
-  // Large frames (PT_CHUNK_BIG_SLOTS slots per lane and more) over trees
-  // larger than two XCD L2s (4 MB each): each queue head deals a contiguous
-  // band of the frame, so an XCD's waves share BVH nodes in its L2 (C5's 17-MB
-  // tree +1.8%, c5big's 68-MB +1.8%); C4's 4-MB tree loses 1.2% to the bands'
-  // uneven ends, and a small frame keeps the interleaved sweep, whose heads
-  // run dry together (C3 -5.5%, its lone launch +12%): profiles/r5/ab_bands*.txt.
-  // PT_QUEUE_BANDS=0/1 forces it (A/B, tests).
-  P.qbands = big_frame && (int64_t)c->n_render_nodes * 128 > ((int64_t)PT_BANDS_TREE_MIB << 20) ? 1 : 0;
-  if (const char* qb = std::getenv("PT_QUEUE_BANDS")) P.qbands = std::atoi(qb) != 0 ? 1 : 0;
-  P.sblocks = (64 * P.n_groups) % P.chunk == 0 ? 1 : 0;  // every (aligned) chunk inside one block
-  // group sums: 12 B per work slot of THIS launch (a rank's share of a split
-  // frame holds only its own blocks' sums)
-  if (nf > 1) {
-    // a frame batch: every render slot's group sums sized at once for the
-    // largest batch of this tile set, and its spill area for the whole grid
-    // (growing a buffer later synchronises the device -- inside the caller's
-    // back-to-back frames)
-    const size_t cap = (size_t)std::max<int64_t>(frame_slots, 1) * 3 *
-                       (size_t)std::max(nf, frames_that_fit(c, tl, PT_MAX_FRAMES));
-    for (int k = 0; k < pt_ctx::kSlots; ++k) {
-      HIPCHK(c->partial[k].reserve(cap));
-      if (c->bvh_stack > PT_STACK)
-        HIPCHK(c->spill[k].reserve((size_t)(c->bvh_stack - PT_STACK) * std::max<int64_t>(want, c->grid_plain) * PT_BLOCK));
+  P.cull_x0 = plan.cull[0];
+  P.cull_y0 = plan.cull[1];
+  P.cull_x1 = plan.cull[2];
+  P.cull_y1 = plan.cull[3];
+  P.group_spp = plan.group_spp;
+  P.group_shift = plan.group_shift;
+  P.n_groups = plan.n_groups;
+  P.grp_m = plan.grp_m;
+  P.grp_sh = plan.grp_sh;
+  P.frame_slots = (uint32_t)plan.frame_slots;
+  P.frm_m = plan.frm_m;
+  P.frm_sh = plan.frm_sh;
+  P.chunk = plan.chunk;
+  P.qbands = plan.qbands;
+  P.sblocks = plan.sblocks;
+  P.shade_batch = plan.shade_batch;
+  P.leaf_weight = plan.leaf_weight;
+  P.drain_div = plan.drain_div;
+  P.tri_only = plan.tri_only;
+  P.helpers = plan.helpers;
+  P.census = plan.census;
+  P.dbg_pix = plan.dbg_pix;
+  P.n_blocks = (int)plan.blocks.size();
+  return P;
+}
+
+// One render: the render kernel on the slot's render stream, then the resolve
+// on the caller's stream `s`, ordered after the render (see pt_ctx: the render
+// pipeline).  (The resolve on the render stream instead measured one frame
+// +0.03 ms: profiles/r5/ab_resolve_reset_stream.txt.)  `nf` > 1: a frame batch
+// (pt_render_frames_device) -- nf frames of these tiles, frame f keyed by
+// seeds[f] into outs[f], in ONE render launch (the MF kernel) and nf resolves;
+// `seeds` null: the parameters' seed.
+// The launch's shape -- tile order, blocks, sample groups, grid, queue claims --
+// is plan_launch's (launch_plan.cpp), from the knobs and the idle query; a
+// plan that is refused returns before anything is enqueued or any slot taken.
+static int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs, int nf, const uint32_t* seeds,
+                  hipStream_t s, uint32_t flags) {
+  std::memset(&c->last, 0, sizeof(c->last));
+  c->times_pending = false;
+  if (tl_in.empty()) return PT_OK;
+  const LaunchKnobs knobs = read_launch_knobs();
+  // A launch that finds every slot's last resolve complete has no frame to
+  // overlap with: it runs on the caller's stream, with no cross-stream waits
+  // in front of the render or between the render and the resolve (a lone
+  // frame's wall clock; the slots still alternate).  Only hipErrorNotReady
+  // means busy: any other result is a fault of an earlier render, reported
+  // here instead of being absorbed into the choice (ADVICE r5).
+  bool gpu_idle = true;  // no earlier render of this context still running or queued
+  for (int k = 0; k < pt_ctx::kSlots && gpu_idle; ++k) {
+    if (!c->ev_free[k]) continue;  // (a slot never used)
+    const hipError_t q = hipEventQuery(c->ev_free[k]);
+    if (q == hipErrorNotReady) {
+      (void)hipGetLastError();  // (a not-ready query is no error of this launch)
+      gpu_idle = false;
+    } else if (q != hipSuccess) {
+      return fail(PT_E_HIP, std::string("render: an earlier launch failed: ") + hipGetErrorString(q));
     }
   }
-  HIPCHK(c->partial[slot].reserve((size_t)std::max<int64_t>(slots, 1) * 3));
-  P.partial = c->partial[slot].p;
-  c->last.partial_bytes = slots * PT_SUM_BYTES;
-  auto log2_exact = [](int v) {  // log2(v) for a power of two, else -1
-    int k = 0;
-    while ((1 << k) < v && k < 30) ++k;
-    return (1 << k) == v ? k : -1;
-  };
-  P.group_shift = log2_exact(P.group_spp);
-  int64_t max_grid = std::max<int64_t>(1, (slots + PT_BLOCK - 1) / PT_BLOCK);
-  int grid = (int)std::min<int64_t>(want, max_grid);
-  if ((stats || P.census) && (size_t)grid * PT_WAVE_TRACE + PT_STATS_SLOTS > c->stats.n)
-    grid = (int)((c->stats.n - PT_STATS_SLOTS) / PT_WAVE_TRACE);
-  grid = std::max(1, grid);
-  if (P.census)  // (a build without -DPT_CENSUS=1 leaves the drain fields 0)
-    HIPCHK(hipMemsetAsync(c->stats.p + PT_STATS_SLOTS, 0, (size_t)grid * PT_WAVE_TRACE * 8, rs));
-  P.stack_spill = nullptr;
-  if (c->bvh_stack > PT_STACK) {  // worst-case depth beyond the LDS stack
-    HIPCHK(c->spill[slot].reserve((size_t)(c->bvh_stack - PT_STACK) * grid * PT_BLOCK));
-    P.stack_spill = c->spill[slot].p;
+  const LaunchPlan plan = plan_launch(plan_input(c, tl_in, nf, flags, gpu_idle, knobs));
+  if (!plan.error.empty()) return fail(PT_E_INVALID, plan.error);
+  // PT_PIPELINE=0 and census launches: every render on the caller's stream, one slot
+  const bool pipelined = knobs.pipeline && !plan.census;
+  const int depth = c->small_last ? pt_ctx::kSlots : pt_ctx::kSlotsLarge;
+  const int slot = pipelined ? (int)(c->slot_rr++ % (uint64_t)depth) : 0;
+  if (!plan.stats) c->small_last = plan.small;
+  const bool idle = pipelined && gpu_idle;
+  if (!c->rstream[slot]) {  // a small launch's first use of slots 2 and 3
+    HIPCHK(make_render_stream(&c->rstream[slot]));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_free[slot], hipEventDisableTiming));
+    HIPCHK(hipEventRecord(c->ev_free[slot], c->stream));
   }
+  hipStream_t rs = pipelined && !idle ? c->rstream[slot] : s;
+  // the slot's device state is free once the previous resolve that read it ran
+  if (!idle) HIPCHK(hipStreamWaitEvent(rs, c->ev_free[slot], 0));
+  const PlanRect* tl = plan.zorder ? plan.ztiles.data() : reinterpret_cast<const PlanRect*>(tl_in.data());
+  const bool tile_out = plan.zorder && (flags & (PT_FLAG_PACKED | PT_FLAG_PACKED16));  // packed outputs keep the caller's tile index
+  if (int rc = sync_list(c->tiles[slot], c->tiles_host[slot], tl, tl_in.size(), rs)) return rc;
+  if (tile_out)
+    if (int rc = sync_list(c->tout[slot], c->tout_host[slot], plan.perm.data(), plan.perm.size(), rs)) return rc;
+  if (int rc = sync_list(c->blocks[slot], c->blocks_host[slot], plan.blocks.data(), plan.blocks.size(), rs)) return rc;
+  if (int rc = sync_list(c->tblock0[slot], c->tblock0_host[slot], plan.tile_block0.data(), plan.tile_block0.size(), rs))
+    return rc;
+  // Queue heads: zeroed by the slot's previous resolve (a memset in front of the render is a dependent launch of its own, ~20 us
+  // before the render kernel starts on a lone frame); a memset only when
+  // that did not happen (first use, a launch that failed half-way)
+  if (!c->counter_clean[slot])
+    HIPCHK(hipMemsetAsync(c->counter[slot].p, 0, PT_QUEUE_WORDS * PT_QUEUE_HEADS * sizeof(uint32_t), rs));
+  c->counter_clean[slot] = false;
+  if (plan.stats) {
+    unsigned long long init[PT_STATS_SLOTS] = {0};
+    init[PT_STAT_WAVE_START_MIN] = init[PT_STAT_WAVE_END_MIN] = init[PT_STAT_WAVE_EMPTY_MIN] = ~0ull;  // atomicMin slots
+    HIPCHK(hipMemcpyAsync(c->stats.p, init, sizeof(init), hipMemcpyHostToDevice, rs));
+    HIPCHK(hipStreamSynchronize(rs));  // `init` is a stack array
+  }
+  KParams P = kernel_params(c, plan, nf, seeds, flags);
+  P.out = outs[0];
+  P.work_counter = c->counter[slot].p;
+  P.n_tiles = (int)tl_in.size();
+  P.tiles = c->tiles[slot].p;
+  P.tile_out = tile_out ? c->tout[slot].p : nullptr;
+  P.blocks = c->blocks[slot].p;
+  P.tile_block0 = c->tblock0[slot].p;
+  // (growing a buffer synchronises the device: a frame batch sizes every render slot's at once)
+  for (int k = 0; k < pt_ctx::kSlots && nf > 1; ++k) {
+    HIPCHK(c->partial[k].reserve(plan.batch_partial_floats));
+    if (plan.batch_spill_ints) HIPCHK(c->spill[k].reserve(plan.batch_spill_ints));
+  }
+  HIPCHK(c->partial[slot].reserve(plan.partial_floats));
+  P.partial = c->partial[slot].p;
+  if (plan.spill_ints) HIPCHK(c->spill[slot].reserve(plan.spill_ints));
+  P.stack_spill = plan.spill_ints ? c->spill[slot].p : nullptr;
+  if (P.census)  // (a build without -DPT_CENSUS=1 leaves the drain fields 0)
+    HIPCHK(hipMemsetAsync(c->stats.p + PT_STATS_SLOTS, 0, (size_t)plan.grid * PT_WAVE_TRACE * 8, rs));
   {
     hipEvent_t* tri = c->ev[c->n_launches % pt_ctx::kRing];
     c->ev0 = tri[0];
@@ -1523,12 +1279,12 @@ static int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs,
     ++c->n_launches;
   }
   HIPCHK(hipEventRecord(c->ev0, rs));
-  HIPCHK(ptk_launch_render(&P, grid, stats, (flags & PT_FLAG_REF_COUNTS) != 0, rs));
+  HIPCHK(ptk_launch_render(&P, plan.grid, plan.stats, (flags & PT_FLAG_REF_COUNTS) != 0, rs));
   HIPCHK(hipEventRecord(c->ev1, rs));
   if (rs != s) HIPCHK(hipStreamWaitEvent(s, c->ev1, 0));  // the resolve reads the finished group sums
   for (int f = 0; f < nf; ++f) {  // (a frame batch: frame f's sums follow frame f - 1's)
     KParams Pf = P;
-    Pf.partial = P.partial + 3 * (size_t)f * (size_t)frame_slots;
+    Pf.partial = P.partial + 3 * (size_t)f * (size_t)plan.frame_slots;
     Pf.out = outs[f];
     HIPCHK(ptk_launch_resolve(&Pf, s));
   }
@@ -1536,15 +1292,17 @@ static int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs,
   HIPCHK(hipEventRecord(c->ev2, s));
   HIPCHK(hipEventRecord(c->ev_free[slot], s));
   c->census_valid = P.census != 0;
-  c->last.grid_blocks = grid;
-  c->last.group_spp = P.group_spp;
-  c->last.blocks_per_cu = (int32_t)(want / std::max(1, c->n_cu));
-  int64_t px = 0;
-  for (const int4& t : tl) px += (int64_t)t.z * t.w;
-  c->last.pixels = px;
+  c->culled_px = plan.culled_px;
+  c->last.tile_zorder = plan.zorder ? 1 : 0;
+  std::copy(plan.footprint, plan.footprint + 4, c->last.footprint);
+  c->last.partial_bytes = plan.slots * PT_SUM_BYTES;
+  c->last.grid_blocks = plan.grid;
+  c->last.group_spp = plan.group_spp;
+  c->last.blocks_per_cu = (int32_t)(plan.want / std::max(1, c->n_cu));
+  c->last.pixels = plan.pixels;
   c->last.bvh_stack = c->bvh_stack;
   c->last.bvh_nodes = (int64_t)c->n_render_nodes;
-  c->last.samples = px * c->params.spp;
+  c->last.samples = plan.pixels * c->params.spp;
   c->last.frames_per_launch = nf;
   return PT_OK;
 }
@@ -1575,31 +1333,34 @@ static int finish_stats(pt_ctx* c, hipStream_t s, uint32_t flags, bool sync) {
   if (counters) {
     unsigned long long v[PT_STATS_SLOTS] = {0};
     HIPCHK(hipMemcpy(v, c->stats.p, sizeof(v), hipMemcpyDeviceToHost));
-    c->last.camera_rays = (int64_t)v[0];
-    c->last.bounce_rays = (int64_t)v[1];
-    c->last.shadow_rays = (int64_t)v[2];
-    c->last.node_visits = (int64_t)v[3];
-    c->last.tri_tests = (int64_t)v[4];
-    c->last.sphere_tests = (int64_t)v[5];
-    c->last.ext_hits = (int64_t)v[6];
-    c->last.wave_trav_steps = (int64_t)v[7];
-    c->last.wave_rounds = (int64_t)v[8];
+    c->last.camera_rays = (int64_t)v[PT_STAT_CAMERA_RAYS];
+    c->last.bounce_rays = (int64_t)v[PT_STAT_BOUNCE_RAYS];
+    c->last.shadow_rays = (int64_t)v[PT_STAT_SHADOW_RAYS];
+    c->last.node_visits = (int64_t)v[PT_STAT_NODE_VISITS];
+    c->last.tri_tests = (int64_t)v[PT_STAT_TRI_TESTS];
+    c->last.sphere_tests = (int64_t)v[PT_STAT_SPHERE_TESTS];
+    c->last.ext_hits = (int64_t)v[PT_STAT_EXT_HITS];
+    c->last.wave_trav_steps = (int64_t)v[PT_STAT_WAVE_TRAV_STEPS];
+    c->last.wave_rounds = (int64_t)v[PT_STAT_WAVE_ROUNDS];
     c->last.culled_samples = c->culled_px * c->params.spp;
-    c->last.leaf_steps = (int64_t)v[9];
-    c->last.queue_atomics = (int64_t)v[10];
-    c->last.shade_clocks = (int64_t)v[11];
-    c->last.trav_clocks = (int64_t)v[12];
-    c->last.max_wave_clocks = (int64_t)v[13];
-    c->last.wave_wall_sum = (int64_t)v[14];
-    c->last.wave_wall_max = (int64_t)v[15];
-    c->last.hitshade_clocks = (int64_t)v[16];
-    for (int k = 0; k < 4; ++k) c->last.section_clocks[k] = (int64_t)v[17 + k];
-    for (int k = 0; k < 4; ++k) c->last.lane_iters[k] = (int64_t)v[27 + k];
-    c->last.deep_stack_steps = (int64_t)v[31];
-    for (int k = 0; k < 32; ++k) c->last.slot_latency_hist[k] = (int64_t)v[32 + k];
-    for (int k = 0; k < 8; ++k) c->last.node_census[k] = (int64_t)v[64 + k];
-    for (int k = 0; k < 3; ++k) c->last.wave_span[k] = (int64_t)(v[22 + k] - v[21]);
-    for (int k = 0; k < 2; ++k) c->last.wave_span[3 + k] = v[25 + k] ? (int64_t)(v[25 + k] - v[21]) : -1;
+    c->last.leaf_steps = (int64_t)v[PT_STAT_LEAF_STEPS];
+    c->last.queue_atomics = (int64_t)v[PT_STAT_QUEUE_ATOMICS];
+    c->last.shade_clocks = (int64_t)v[PT_STAT_SHADE_CLOCKS];
+    c->last.trav_clocks = (int64_t)v[PT_STAT_TRAV_CLOCKS];
+    c->last.max_wave_clocks = (int64_t)v[PT_STAT_MAX_WAVE_CLOCKS];
+    c->last.wave_wall_sum = (int64_t)v[PT_STAT_WAVE_WALL_SUM];
+    c->last.wave_wall_max = (int64_t)v[PT_STAT_WAVE_WALL_MAX];
+    c->last.hitshade_clocks = (int64_t)v[PT_STAT_HITSHADE_CLOCKS];
+    for (int k = 0; k < 4; ++k) c->last.section_clocks[k] = (int64_t)v[PT_STAT_SECTION_CLOCKS + k];
+    for (int k = 0; k < 4; ++k) c->last.lane_iters[k] = (int64_t)v[PT_STAT_LANE_ITERS + k];
+    c->last.deep_stack_steps = (int64_t)v[PT_STAT_DEEP_STACK_STEPS];
+    for (int k = 0; k < 32; ++k) c->last.slot_latency_hist[k] = (int64_t)v[PT_STAT_SLOT_LATENCY_HIST + k];
+    for (int k = 0; k < 8; ++k) c->last.node_census[k] = (int64_t)v[PT_STAT_NODE_CENSUS + k];
+    // the launch's shape, from the first wave's start: last start, first / last end, first / last empty queue (-1: never)
+    const unsigned long long t0 = v[PT_STAT_WAVE_START_MIN];
+    for (int k = 0; k < 3; ++k) c->last.wave_span[k] = (int64_t)(v[PT_STAT_WAVE_START_MAX + k] - t0);
+    for (int k = 0; k < 2; ++k)
+      c->last.wave_span[3 + k] = v[PT_STAT_WAVE_EMPTY_MIN + k] ? (int64_t)(v[PT_STAT_WAVE_EMPTY_MIN + k] - t0) : -1;
     c->last.counters_valid = 1;
   }
   return PT_OK;
@@ -1986,39 +1747,6 @@ int pt_to_color_device(pt_ctx* c, const float* hdr_dev, int32_t width, int32_t h
   return PT_OK;
 }
 
-// Frames of the tile set `tl` one launch of a frame batch takes.  A frame
-// with more than PT_BATCH_SLOTS work slots per lane of a whole MI355X renders
-// alone: it fills the GPU by itself, and batching measured slower there (C4
-// -4.7%; C3's 25.6 slots per lane +2%, its strong split's shares +15..+45%:
-// profiles/r6/ab_frame_batch.txt).  Otherwise as many as keep the work-slot
-// indices (with the claims' overshoot, a grid of up to 40 waves per CU) 32-bit
-// and the group sums within PT_GROUP_SUM_GIB.  The blocks are the launch's
-// own (the tiles' 8x8 blocks inside the scene's screen footprint).
-static int frames_that_fit(const pt_ctx* c, const std::vector<int4>& tl, int nf) {
-  const int W = c->params.width, H = c->params.height;
-  KParams fp;
-  std::memset(&fp, 0, sizeof(fp));
-  fp.W = W;
-  fp.H = H;
-  screen_footprint(c, fp);
-  int64_t blocks = 0;
-  for (const int4& t : tl) {
-    const int x0 = std::max(t.x, fp.cull_x0), x1 = std::min(t.x + t.z - 1, fp.cull_x1);
-    const int y0 = std::max(t.y, fp.cull_y0), y1 = std::min(t.y + t.w - 1, fp.cull_y1);
-    if (x1 >= x0 && y1 >= y0) blocks += (int64_t)((x1 - x0 + 8) / 8) * ((y1 - y0 + 8) / 8);
-  }
-  const int64_t frame_blocks = (int64_t)((W + 7) / 8) * ((H + 7) / 8);
-  const int64_t waves = std::max<int64_t>({(int64_t)c->grid_plain, (int64_t)c->grid_stats, (int64_t)40 * c->n_cu});
-  const int gs = group_size(traced_px(c, W, H), c->env_w > 0, c->params.spp, (int64_t)PT_GROUP_REF_LANES,
-                            frame_blocks, waves);
-  const int64_t per = blocks * 64 * ((c->params.spp + gs - 1) / gs);
-  if (per > (int64_t)PT_BATCH_SLOTS * PT_GROUP_REF_LANES) return 1;
-  while (nf > 1 && (per * nf + 2 * waves * PT_CHUNK_BIG >= (int64_t)INT32_MAX ||
-                    per * nf * PT_SUM_BYTES > ((int64_t)PT_GROUP_SUM_GIB << 30)))
-    --nf;
-  return nf;
-}
-
 int pt_render_frames_device(pt_ctx* c, const pt_tile* tiles, int32_t n_tiles, int32_t n_frames, const uint32_t* seeds,
                             float* const* hdr_outs_dev, void* stream, uint32_t flags) {
   int rc = check_ready(c);
@@ -2038,10 +1766,9 @@ int pt_render_frames_device(pt_ctx* c, const pt_tile* tiles, int32_t n_tiles, in
   // One launch for the batch in the plain common build; the environment-light
   // and global-table builds, diagnostics and PT_FRAME_BATCH=0 render the
   // frames one launch each (the same images)
-  static const bool batch_on = !std::getenv("PT_FRAME_BATCH") || std::atoi(std::getenv("PT_FRAME_BATCH")) != 0;
-  const bool gtab = c->n_bsdfs > PT_LDS_BSDFS || c->n_lights > PT_LDS_LIGHTS || std::getenv("PT_FORCE_GLOBAL_TABLES");
-  const bool one = !batch_on || n_frames == 1 || c->env_w > 0 || gtab || std::getenv("PT_CENSUS") ||
-                   std::getenv("PT_DEBUG_PIXEL");
+  const LaunchKnobs knobs = read_launch_knobs();
+  const PlanInput in = plan_input(c, tl, 1, flags, true, knobs);
+  const bool one = !knobs.frame_batch || n_frames == 1 || in.env || global_tables(in) || knobs.census || knobs.debug_pixel;
   if (one) {
     for (int32_t f = 0; f < n_frames; ++f)
       if ((rc = launch(c, tl, &hdr_outs_dev[f], 1, &seeds[f], s, flags))) return rc;
@@ -2049,7 +1776,7 @@ int pt_render_frames_device(pt_ctx* c, const pt_tile* tiles, int32_t n_tiles, in
     // (frames beyond what one launch's slot indices and group sums hold go
     // into further batches)
     for (int32_t f = 0; f < n_frames;) {
-      const int nf = frames_that_fit(c, tl, n_frames - f);
+      const int nf = frames_that_fit(in, n_frames - f);
       if ((rc = launch(c, tl, hdr_outs_dev + f, nf, seeds + f, s, flags))) return rc;
       f += nf;
     }

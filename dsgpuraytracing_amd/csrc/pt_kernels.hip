@@ -1236,7 +1236,7 @@ __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_PER_SIMD) void render_kernel
         // the XCD L2s are not coherent; PT_QUEUE_HEADS of them, a wave starting
         // at its XCD's) refills it.  The claim size (128 / 256 / 512) and the
         // heads' dealing (interleaved chunks or contiguous bands) are chosen
-        // on the host per launch (pt_api.cpp launch; profiles/r5/ab_chunk_*.txt,
+        // on the host per launch (launch_plan.cpp; profiles/r5/ab_chunk_*.txt,
         // ab_queue_heads.txt, ab_bands*.txt).
         uint32_t cnt = (uint32_t)__popcll(m);
         uint32_t avail = chunk_end - chunk_next;
@@ -1630,19 +1630,19 @@ __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_PER_SIMD) void render_kernel
 #endif
   if (STATS) {
     PT_STAMP(S_OTHER);
-    unsigned long long v[11] = {n_cam, n_bounce, n_shadow, ct.nodes, ct.tris, ct.spheres, n_hits,
+    unsigned long long v[PT_STAT_LANE_SUMS] = {n_cam, n_bounce, n_shadow, ct.nodes, ct.tris, ct.spheres, n_hits,
                                 n_titer, n_rounds, n_leafit, n_atomics};
-    for (int k = 0; k < 11; ++k) {
+    for (int k = 0; k < PT_STAT_LANE_SUMS; ++k) {
       unsigned long long s = v[k];
       for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-      if (lane == 0) atomicAdd(P.stats + k, s);
+      if (lane == 0) atomicAdd(P.stats + PT_STAT_CAMERA_RAYS + k, s);
     }
-    if (lane < 32) atomicAdd(P.stats + 32 + lane, (unsigned long long)s_hist[lane]);
+    if (lane < 32) atomicAdd(P.stats + PT_STAT_SLOT_LATENCY_HIST + lane, (unsigned long long)s_hist[lane]);
     const uint32_t li[5] = {l_other, l_ready, l_dead, l_leaf, l_deep};
     for (int k = 0; k < 5; ++k) {
       unsigned long long s = li[k];
       for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off);
-      if (lane == 0) atomicAdd(P.stats + 27 + k, s);
+      if (lane == 0) atomicAdd(P.stats + PT_STAT_LANE_ITERS + k, s);  // (the fifth: PT_STAT_DEEP_STACK_STEPS)
     }
     // load balance: the slowest wave bounds the launch
     w_empty = w_empty ? w_empty : ~0ull;
@@ -1665,25 +1665,25 @@ __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_PER_SIMD) void render_kernel
       const unsigned long long trav = s_clk[S_TRAV];
       const unsigned long long hitshade = s_clk[S_HIT] + s_clk[S_NEE] + s_clk[S_BSDF];
       const unsigned long long shade = hitshade + s_clk[S_FETCH] + s_clk[S_CAMERA] + s_clk[S_OTHER];
-      atomicAdd(P.stats + 11, shade);
-      atomicAdd(P.stats + 12, trav);
-      atomicMax(P.stats + 13, shade + trav);
-      atomicAdd(P.stats + 16, hitshade);
-      for (int k = 0; k < 4; ++k) atomicAdd(P.stats + 17 + k, s_clk[S_HIT + k]);
+      atomicAdd(P.stats + PT_STAT_SHADE_CLOCKS, shade);
+      atomicAdd(P.stats + PT_STAT_TRAV_CLOCKS, trav);
+      atomicMax(P.stats + PT_STAT_MAX_WAVE_CLOCKS, shade + trav);
+      atomicAdd(P.stats + PT_STAT_HITSHADE_CLOCKS, hitshade);
+      for (int k = 0; k < 4; ++k) atomicAdd(P.stats + PT_STAT_SECTION_CLOCKS + k, s_clk[S_HIT + k]);
       unsigned long long w = wall_clock64() - w_start;
       const unsigned long long w_end = wall_clock64();  // launch shape: first/last wave start and end
-      atomicMin(P.stats + 21, w_start);
-      atomicMax(P.stats + 22, w_start);
-      atomicMin(P.stats + 23, w_end);
-      atomicMax(P.stats + 24, w_end);
+      atomicMin(P.stats + PT_STAT_WAVE_START_MIN, w_start);
+      atomicMax(P.stats + PT_STAT_WAVE_START_MAX, w_start);
+      atomicMin(P.stats + PT_STAT_WAVE_END_MIN, w_end);
+      atomicMax(P.stats + PT_STAT_WAVE_END_MAX, w_end);
       if (w_empty != ~0ull) {
-        atomicMin(P.stats + 25, w_empty);
-        atomicMax(P.stats + 26, w_empty);
+        atomicMin(P.stats + PT_STAT_WAVE_EMPTY_MIN, w_empty);
+        atomicMax(P.stats + PT_STAT_WAVE_EMPTY_MAX, w_empty);
       }
-      atomicAdd(P.stats + 14, w);
-      atomicMax(P.stats + 15, w);
+      atomicAdd(P.stats + PT_STAT_WAVE_WALL_SUM, w);
+      atomicMax(P.stats + PT_STAT_WAVE_WALL_MAX, w);
       const uint32_t cn[8] = {c_wsteps, c_uniform, c_cover, c_lanes, c_top2w, c_top2l, c_top3w, c_top3l};
-      for (int k = 0; k < 8; ++k) atomicAdd(P.stats + 64 + k, (unsigned long long)cn[k]);
+      for (int k = 0; k < 8; ++k) atomicAdd(P.stats + PT_STAT_NODE_CENSUS + k, (unsigned long long)cn[k]);
       // per-wave trace (pt_get_wave_trace): start, first empty queue, end,
       // (XCC id << 32 | HW_ID), camera samples
       unsigned long long* tw = P.stats + PT_STATS_SLOTS + PT_WAVE_TRACE * (size_t)wave_id;

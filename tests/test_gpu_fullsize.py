@@ -211,7 +211,7 @@ def test_fullsize_sampled_tiles_match_oracle(tmp_path, restate, name, k, k_mixed
 @pytest.mark.parametrize("name,spp", [("c3", 64), ("c4", 16)])
 def test_footprint_cull_exact_at_full_size(monkeypatch, name, spp):
     """The headline's default camera leaves most of the frame outside the
-    scene box's screen footprint (pt_api.cpp screen_footprint): those samples
+    scene box's screen footprint (launch_plan.cpp screen_footprint): those samples
     are not traced (camera.cpp:113-129 rays that miss the root box see
     nothing, pathtracer.cpp:421-426).  The culled frame must equal the frame
     traced sample by sample (PT_NO_FOOTPRINT_CULL=1) bit for bit, edges and
@@ -286,7 +286,7 @@ def test_c4_fullsize_eight_way_split_bit_identical():
 
 
 def test_c3_small_launch_shape_never_changes_values(monkeypatch):
-    """The small-launch shape (pt_api.cpp launch: a strong split's share has
+    """The small-launch shape (launch_plan.cpp plan_launch: a strong split's share has
     few work slots per lane, so it claims 64 slots at a time and, queued
     behind other frames, runs on half the resident grid with up to four
     frames in flight) changes only which wave renders which slot: the C3

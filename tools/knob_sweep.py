@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Diagnostic: render-kernel time under the launch tuning knobs (environment
-variables read per launch by pt_api.cpp: PT_WAVES_PER_CU, PT_SHADE_BATCH,
-PT_SAMPLE_GROUP, PT_LEAF_WEIGHT), for the whole frame and for one rank's
+variables read per launch by csrc/launch_plan.cpp read_launch_knobs; the
+field comments of LaunchKnobs in csrc/launch_plan.h are the knob table:
+PT_WAVES_PER_CU, PT_SHADE_BATCH, PT_SAMPLE_GROUP, PT_LEAF_WEIGHT, ...), for the whole frame and for one rank's
 share of an N-GPU split.
 Usage: python tools/knob_sweep.py --workload c3 --share 8 \
          --grid "PT_WAVES_PER_CU=12,16,20" --grid "PT_SAMPLE_GROUP=1,2" """
