@@ -25,6 +25,7 @@
 
 #include "../../include/ptgpu.h"
 #include "../../include/ptgpu_scene.h"
+#include "denoise.h"
 #include "film.h"
 #include "launch_plan.h"
 #include "pt_device.h"
@@ -296,6 +297,17 @@ struct pt_ctx {
   std::vector<pt_film*> films;  // films not yet destroyed (pt_destroy frees them)
   DevBuf<uint32_t> tc_thr;      // pt_to_color_thresholds on the device (uploaded at first use)
   bool tc_thr_ready = false;
+  // first-hit feature pass (pt_render_features*): its tile list, stack spill
+  // area and the device side of the host entry point's output; a pass that
+  // comes on another stream than the last waits for the last one's event
+  DevBuf<int4> ftiles;
+  std::vector<int4> ftiles_host;
+  DevBuf<int> f_spill;
+  DevBuf<float4> feat_out;
+  hipEvent_t ev_feat = nullptr;
+  hipStream_t feat_stream = nullptr;
+  bool feat_ordered = false;
+  DevBuf<float4> dn_a, dn_b;  // pt_denoise_device: the iterations' ping-pong records (grown on demand)
 };
 
 // A progressive film (ptgpu.h: pt_film_*; kernels and record layout: film.h).
@@ -310,6 +322,9 @@ struct pt_film {
   DevBuf<float> emax;
   DevBuf<float> out_hdr, out_err;  // pt_film_resolve: device side of the host outputs
   DevBuf<uint32_t> out_rgba;
+  DevBuf<float4> feat;   // 2 * W * H feature records (pt_film_set_features; allocated at first use)
+  DevBuf<float4> cv[2];  // the denoiser's working records (allocated at first use)
+  bool have_feat = false;  // set since creation / the last clear
   uint64_t next = 0;     // next sample index (<= 2^32)
   int64_t passes = 0;
   hipEvent_t ev_acc[2] = {}, ev_res[2] = {};  // around the last accumulate / resolve kernel
@@ -380,6 +395,12 @@ int pt_destroy(pt_ctx* c) {
   for (pt_film* f : c->films) film_free(f);
   c->films.clear();
   c->tc_thr.release();
+  c->ftiles.release();
+  c->f_spill.release();
+  c->feat_out.release();
+  c->dn_a.release();
+  c->dn_b.release();
+  if (c->ev_feat) (void)hipEventDestroy(c->ev_feat);
   c->nodes.release();
   c->nodes2.release();
   c->prim_map.release();
@@ -1467,6 +1488,9 @@ static void film_free(pt_film* f) {
   f->out_hdr.release();
   f->out_err.release();
   f->out_rgba.release();
+  f->feat.release();
+  f->cv[0].release();
+  f->cv[1].release();
   for (hipEvent_t e : {f->ev_acc[0], f->ev_acc[1], f->ev_res[0], f->ev_res[1], f->ev_order})
     if (e) (void)hipEventDestroy(e);
   delete f;
@@ -1557,6 +1581,7 @@ int pt_film_clear(pt_film* f, void* stream) {
   HIPCHK(hipMemsetAsync(f->rec.p, 0, 2 * (size_t)f->W * (size_t)f->H * sizeof(uint4), s));
   f->next = 0;
   f->passes = 0;
+  f->have_feat = false;
   return film_end(f, s);
 }
 
@@ -1744,6 +1769,221 @@ int pt_to_color_device(pt_ctx* c, const float* hdr_dev, int32_t width, int32_t h
   a.rgba = rgba_dev;
   a.W = width;
   HIPCHK(ptk_to_color(&a, stream ? (hipStream_t)stream : c->stream));
+  return PT_OK;
+}
+
+// ---- first-hit feature buffers (ptgpu.h: pt_render_features*; kernel: pt_kernels.hip features_kernel)
+static int features_launch(pt_ctx* c, const std::vector<int4>& tl, float4* feat, hipStream_t s) {
+  if (tl.empty()) return PT_OK;
+  if (!c->ev_feat) HIPCHK(hipEventCreateWithFlags(&c->ev_feat, hipEventDisableTiming));
+  // the tile list and the spill area are the context's: a pass on another
+  // stream than the last one's waits for it
+  if (c->feat_ordered && c->feat_stream != s) HIPCHK(hipStreamWaitEvent(s, c->ev_feat, 0));
+  if (int rc = sync_list(c->ftiles, c->ftiles_host, tl.data(), tl.size(), s)) return rc;
+  FeatArgs A;
+  std::memset(&A, 0, sizeof(A));
+  for (int k = 0; k < 3; ++k) {
+    A.cam_pos[k] = (float)c->cam.pos[k];
+    A.c2w_col0[k] = (float)c->cam.c2w[3 * k + 0];
+    A.c2w_col1[k] = (float)c->cam.c2w[3 * k + 1];
+    A.c2w_col2[k] = (float)c->cam.c2w[3 * k + 2];
+  }
+  A.cam_ax = (float)(c->cam.screen_w / c->cam.screen_dist);
+  A.cam_ay = (float)(c->cam.screen_h / c->cam.screen_dist);
+  A.W = c->params.width;
+  A.H = c->params.height;
+  A.inv_w = 1.0f / (float)A.W;
+  A.inv_h = 1.0f / (float)A.H;
+  A.nodes = c->nodes.p;
+  A.prims = c->prims.p;
+  A.norms = c->norms.p;
+  A.tiles = c->ftiles.p;
+  A.feat = feat;
+  if (c->bvh_stack > PT_STACK) {
+    HIPCHK(c->f_spill.reserve((size_t)(c->bvh_stack - PT_STACK) * tl.size() * 16 * PT_BLOCK));
+    A.stack_spill = c->f_spill.p;
+  }
+  HIPCHK(ptk_launch_features(&A, (int)tl.size(), s));
+  HIPCHK(hipEventRecord(c->ev_feat, s));
+  c->feat_stream = s;
+  c->feat_ordered = true;
+  return PT_OK;
+}
+
+int pt_render_features_device(pt_ctx* c, const pt_tile* tiles, int32_t n_tiles, void* feat_dev, void* stream) {
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = tile_launch(c))) return rc;
+  if (n_tiles < 0 || (n_tiles > 0 && (!tiles || !feat_dev)))
+    return fail(PT_E_INVALID, "pt_render_features_device: bad args");
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<int4> tl;
+  if ((rc = build_tiles(c, tiles, n_tiles, tl))) return rc;
+  return features_launch(c, tl, (float4*)feat_dev, stream ? (hipStream_t)stream : c->stream);
+}
+
+int pt_render_features(pt_ctx* c, const pt_tile* tiles, int32_t n_tiles, void* feat_host) {
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if ((rc = tile_launch(c))) return rc;
+  if (n_tiles < 0 || (n_tiles > 0 && (!tiles || !feat_host))) return fail(PT_E_INVALID, "pt_render_features: bad args");
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<int4> tl;
+  if ((rc = build_tiles(c, tiles, n_tiles, tl))) return rc;
+  const size_t W = (size_t)c->params.width, H = (size_t)c->params.height;
+  HIPCHK(c->feat_out.reserve(2 * W * H));
+  if ((rc = features_launch(c, tl, c->feat_out.p, c->stream))) return rc;
+  // only the tiles' records go back: the caller's buffer is theirs outside them
+  for (const int4& t : tl)
+    for (size_t plane = 0; plane < 2; ++plane) {
+      const size_t off = plane * W * H + (size_t)t.y * W + (size_t)t.x;
+      HIPCHK(hipMemcpy2DAsync((float4*)feat_host + off, W * sizeof(float4), c->feat_out.p + off, W * sizeof(float4),
+                              (size_t)t.z * sizeof(float4), (size_t)t.w, hipMemcpyDeviceToHost, c->stream));
+    }
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return PT_OK;
+}
+
+// ---- the denoiser (ptgpu.h: pt_denoise_*, pt_film_denoise*; kernels: denoise.hip)
+int pt_denoise_params_default(pt_denoise_params* out) {
+  if (!out) return fail(PT_E_INVALID, "pt_denoise_params_default: out is NULL");
+  out->iterations = 5;
+  out->normal_squarings = 7;
+  out->sigma_l = 4.0f;
+  out->sigma_p = PT_DENOISE_SIGMA_P;
+  return PT_OK;
+}
+
+// The parameters a call runs with: the defaults for NULL, else the caller's, checked.
+static int denoise_params(const pt_denoise_params* in, pt_denoise_params* out, const char* fn) {
+  if (!in) return pt_denoise_params_default(out);
+  if (in->iterations < 1 || in->iterations > 6)
+    return fail(PT_E_INVALID, std::string(fn) + ": iterations must be 1 .. 6");
+  if (in->normal_squarings < 0 || in->normal_squarings > 10)
+    return fail(PT_E_INVALID, std::string(fn) + ": normal_squarings must be 0 .. 10");
+  if (!(in->sigma_l > 0.0f) || !(in->sigma_p > 0.0f))
+    return fail(PT_E_INVALID, std::string(fn) + ": sigma_l and sigma_p must be > 0");
+  *out = *in;
+  return PT_OK;
+}
+
+// The iterations: `in` -> s0 -> s1 -> s0 ... with the last one into `out`.
+static int denoise_chain(const float4* in, const float4* feat, int W, int H, const pt_denoise_params& prm, float4* s0,
+                         float4* s1, float4* out, hipStream_t s) {
+  DenoiseIterArgs a;
+  a.feat = feat;
+  a.W = W;
+  a.H = H;
+  a.normal_squarings = prm.normal_squarings;
+  a.sigma_l = prm.sigma_l;
+  a.sigma_p = prm.sigma_p;
+  const float4* src = in;
+  for (int i = 0; i < prm.iterations; ++i) {
+    a.in = src;
+    a.out = i == prm.iterations - 1 ? out : (i & 1) ? s1 : s0;
+    a.step = 1 << i;
+    HIPCHK(ptk_denoise_iteration(&a, s));
+    src = a.out;
+  }
+  return PT_OK;
+}
+
+int pt_denoise_device(pt_ctx* c, const float* cv_dev, const void* feat_dev, int32_t width, int32_t height,
+                      const pt_denoise_params* params, float* out_cv_dev, void* stream) {
+  pt_denoise_params prm;
+  if (int rc = denoise_params(params, &prm, "pt_denoise_device")) return rc;
+  if (!c || !cv_dev || !feat_dev || !out_cv_dev) return fail(PT_E_INVALID, "pt_denoise_device: NULL argument");
+  if (width < 1 || height < 1 || width > 65535 || height > 65535 || (int64_t)width * height > (int64_t)1 << 30)
+    return fail(PT_E_INVALID, "pt_denoise_device: width and height must be 1 .. 65535 and width * height <= 2^30");
+  const size_t px = (size_t)width * (size_t)height;
+  const uintptr_t a0 = (uintptr_t)cv_dev, b0 = (uintptr_t)out_cv_dev, len = px * sizeof(float4);
+  if (a0 < b0 + len && b0 < a0 + len) return fail(PT_E_INVALID, "pt_denoise_device: input and output overlap");
+  HIPCHK(hipSetDevice(c->device));
+  if (prm.iterations > 1) FILM_ALLOC(c->dn_a.reserve(px));
+  if (prm.iterations > 2) FILM_ALLOC(c->dn_b.reserve(px));
+  return denoise_chain((const float4*)cv_dev, (const float4*)feat_dev, width, height, prm, c->dn_a.p, c->dn_b.p,
+                       (float4*)out_cv_dev, stream ? (hipStream_t)stream : c->stream);
+}
+
+static int film_frame_check(const pt_film* f, const char* fn) {
+  const pt_params& P = f->ctx->params;
+  if (P.width != f->W || P.height != f->H)
+    return fail(PT_E_INVALID, std::string(fn) + ": pt_params frame " + std::to_string(P.width) + " x " +
+                                  std::to_string(P.height) + " differs from the film's " + std::to_string(f->W) + " x " +
+                                  std::to_string(f->H));
+  return PT_OK;
+}
+
+int pt_film_set_features(pt_film* f, const pt_tile* tiles, int32_t n_tiles, void* stream) {
+  if (!f) return fail(PT_E_INVALID, "pt_film_set_features: NULL film");
+  pt_ctx* c = f->ctx;
+  int rc = check_ready(c);
+  if (rc) return rc;
+  if (n_tiles < 0 || (n_tiles > 0 && !tiles)) return fail(PT_E_INVALID, "pt_film_set_features: bad args");
+  if ((rc = film_frame_check(f, "pt_film_set_features"))) return rc;
+  if ((rc = tile_launch(c))) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<int4> tl;
+  if ((rc = build_tiles(c, tiles, n_tiles, tl))) return rc;
+  FILM_ALLOC(f->feat.reserve(2 * (size_t)f->W * (size_t)f->H));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if ((rc = film_begin(f, s))) return rc;
+  if (!f->have_feat) HIPCHK(ptk_features_clear(f->feat.p, f->W, f->H, s));  // a pixel never covered: the miss record
+  if ((rc = features_launch(c, tl, f->feat.p, s))) return rc;
+  f->have_feat = true;
+  return film_end(f, s);
+}
+
+int pt_film_denoise_device(pt_film* f, const pt_denoise_params* params, float* hdr_dev, uint32_t* rgba_dev,
+                           void* stream) {
+  if (!f) return fail(PT_E_INVALID, "pt_film_denoise_device: NULL film");
+  pt_denoise_params prm;
+  if (int rc = denoise_params(params, &prm, "pt_film_denoise_device")) return rc;
+  if (!f->have_feat)
+    return fail(PT_E_INVALID, "pt_film_denoise_device: no features (pt_film_set_features after creation / pt_film_clear)");
+  if (int rc = film_frame_check(f, "pt_film_denoise_device")) return rc;
+  if (!hdr_dev && !rgba_dev) return PT_OK;
+  pt_ctx* c = f->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t px = (size_t)f->W * (size_t)f->H;
+  FILM_ALLOC(f->cv[0].reserve(px));
+  FILM_ALLOC(f->cv[1].reserve(px));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (int rc = film_begin(f, s)) return rc;
+  DenoisePrepareArgs pa;
+  pa.rec = f->rec.p;
+  pa.cv = f->cv[0].p;
+  pa.W = f->W;
+  pa.H = f->H;
+  HIPCHK(ptk_denoise_prepare(&pa, s));
+  // cv[0] -> cv[1] -> cv[0] ...: the result is in cv[iterations & 1]
+  float4* res = f->cv[prm.iterations & 1].p;
+  if (int rc = denoise_chain(f->cv[0].p, f->feat.p, f->W, f->H, prm, f->cv[1].p, f->cv[0].p, res, s)) return rc;
+  DenoiseFinishArgs fa;
+  fa.cv = res;
+  fa.thr = c->tc_thr.p;
+  fa.hdr = hdr_dev;
+  fa.rgba = rgba_dev;
+  fa.W = f->W;
+  fa.H = f->H;
+  HIPCHK(ptk_denoise_finish(&fa, s));
+  return film_end(f, s);
+}
+
+int pt_film_denoise(pt_film* f, const pt_denoise_params* params, float* hdr_host, uint32_t* rgba_host) {
+  if (!f) return fail(PT_E_INVALID, "pt_film_denoise: NULL film");
+  pt_ctx* c = f->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t px = (size_t)f->W * (size_t)f->H;
+  if (hdr_host) FILM_ALLOC(f->out_hdr.reserve(3 * px));
+  if (rgba_host) FILM_ALLOC(f->out_rgba.reserve(px));
+  if (int rc = pt_film_denoise_device(f, params, hdr_host ? f->out_hdr.p : nullptr,
+                                      rgba_host ? f->out_rgba.p : nullptr, nullptr))
+    return rc;
+  hipStream_t s = c->stream;
+  if (hdr_host) HIPCHK(hipMemcpyAsync(hdr_host, f->out_hdr.p, 3 * px * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (rgba_host) HIPCHK(hipMemcpyAsync(rgba_host, f->out_rgba.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
   return PT_OK;
 }
 

@@ -246,3 +246,21 @@ extern "C" hipError_t ptk_launch_intersect(const DNode* nodes, const DPrim* prim
                                            const float* maxt, int64_t n, int32_t* hit, float* t, int32_t* prim,
                                            int32_t* anyhit, int* spill, const int* prim_map, hipStream_t s);
 extern "C" hipError_t ptk_render_occupancy(int* waves_per_cu, bool stats, bool env, bool gtab);
+
+// First-hit feature pass (features_kernel; ptgpu.h pt_render_features_device):
+// the camera as KParams holds it, the render tree, and the output records.
+struct FeatArgs {
+  float cam_pos[3];
+  float c2w_col0[3], c2w_col1[3], c2w_col2[3];
+  float cam_ax, cam_ay;
+  float inv_w, inv_h;
+  int W, H;
+  const DNode* nodes;
+  const DPrim* prims;
+  const float* norms;
+  const int4* tiles;  // (x, y, w, h), each <= 32 x 32 and inside the frame
+  float4* feat;       // 2 * W * H records: {N, bsdf}, then {P, z}
+  int* stack_spill;   // traversal stack entries beyond PT_STACK (null if the BVH never needs them)
+};
+// One wave per 64 pixels (an 8x8 block row pair) of each tile: n_tiles * 16 workgroups.
+extern "C" hipError_t ptk_launch_features(const FeatArgs* a, int n_tiles, hipStream_t s);

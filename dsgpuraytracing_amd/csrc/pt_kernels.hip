@@ -1793,6 +1793,67 @@ __global__ __launch_bounds__(PT_BLOCK) void intersect_kernel(const DNode* __rest
   anyhit[i] = a ? 1 : 0;
 }
 
+// The hit record of the shading phase (render_kernel: "hit record"), restated
+// for the feature pass: the hit point rebuilt from the primitive, the shading
+// normal interpolated and, for a triangle, flipped to face the ray.
+__device__ __forceinline__ void first_hit_record(const DPrim* __restrict__ prims, const float* __restrict__ norms,
+                                                 float3 o, float3 d, const Hit& h, float3& hp, float3& ns,
+                                                 int& bsdf) {
+  const DPrim pr = prims[h.prim];
+  float nn[9];
+  for (int k = 0; k < 9; ++k) nn[k] = norms[9 * (size_t)h.prim + k];
+  const int meta = __float_as_int(pr.v0.w);  // (bsdf << 1) | is_triangle
+  bsdf = meta >> 1;
+  if (meta & 1) {
+    float3 V0 = f3(pr.v0.x, pr.v0.y, pr.v0.z), E1 = f3(pr.e1.x, pr.e1.y, pr.e1.z), E2 = f3(pr.e2.x, pr.e2.y, pr.e2.z);
+    float hu, hv, ht;
+    mt_terms(o, d, V0, E1, E2, hu, hv, ht);  // the barycentrics of the traversal test
+    float w0 = 1.0f - hu - hv;
+    hp = V0 + E1 * hu + E2 * hv;
+    ns = ld3(nn) * w0 + ld3(nn + 3) * hu + ld3(nn + 6) * hv;
+    if (dot(d, ns) > 0.0f) ns = f3(0, 0, 0) - ns;
+  } else {
+    float3 C = f3(pr.v0.x, pr.v0.y, pr.v0.z);
+    ns = normalize(o + d * h.t - C);
+    hp = C + ns * pr.e1.x;
+  }
+}
+
+// First-hit feature records of the listed tiles (ptgpu.h: pt_render_features_device):
+// one lane per pixel, one wave per 8x8 pixel block of a tile (coherent rays),
+// the ray of render_kernel's camera_ray through the pixel centre.
+__global__ __launch_bounds__(PT_BLOCK) void features_kernel(FeatArgs A) {
+  __shared__ int s_stack[PT_STACK * PT_BLOCK];
+  const Stack stk{(lds_int*)(s_stack + threadIdx.x), A.stack_spill, gridDim.x * PT_BLOCK};
+  const int4 tile = A.tiles[blockIdx.x >> 4];
+  const int2 px = tile_pixel(tile, (blockIdx.x & 15u) * PT_BLOCK + threadIdx.x);
+  if (px.x < 0 || px.x >= A.W || px.y >= A.H) return;
+  float fx = ((float)px.x + 0.5f) * A.inv_w;
+  float fy = ((float)px.y + 0.5f) * A.inv_h;
+  float3 sp = f3((0.5f - fx) * A.cam_ax, (0.5f - fy) * A.cam_ay, 1.0f);
+  float3 wsp = ld3(A.c2w_col0) * sp.x + ld3(A.c2w_col1) * sp.y + ld3(A.c2w_col2) * sp.z;
+  const float3 d = normalize(f3(0, 0, 0) - wsp);
+  const float3 o = wsp + ld3(A.cam_pos);
+  Hit h;
+  h.t = 0;
+  h.prim = -1;
+  Counters ct = {0, 0, 0};
+  const bool found = traverse<false>(A.nodes, A.prims, stk, o, d, 3.0e38f, false, h, ct);
+  float4 r0 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1)), r1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if (found) {
+    float3 hp, ns;
+    int bsdf;
+    first_hit_record(A.prims, A.norms, o, d, h, hp, ns, bsdf);
+    const float l2 = dot(ns, ns);
+    const float3 n = l2 > 0.0f ? ns * __builtin_amdgcn_rsqf(l2) : f3(0, 0, 0);
+    r0 = make_float4(n.x, n.y, n.z, __int_as_float(bsdf));
+    r1 = make_float4(hp.x, hp.y, hp.z, h.t);
+  }
+  const size_t p = (size_t)px.x + (size_t)px.y * (size_t)A.W;
+  A.feat[p] = r0;
+  A.feat[(size_t)A.W * (size_t)A.H + p] = r1;
+}
+
 #endif  // !PT_ENV_TU
 
 }  // namespace ptk
@@ -1869,6 +1930,12 @@ extern "C" hipError_t ptk_launch_intersect(const DNode* nodes, const DPrim* prim
   if (grid == 0) return hipSuccess;
   hipLaunchKernelGGL(ptk::intersect_kernel, dim3(grid), dim3(PT_BLOCK), 0, s, nodes, prims, o, d, maxt, n,
                      hit, t, prim, anyhit, spill, prim_map);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t ptk_launch_features(const FeatArgs* a, int n_tiles, hipStream_t s) {
+  if (n_tiles <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ptk::features_kernel, dim3((unsigned)n_tiles * 16u), dim3(PT_BLOCK), 0, s, *a);
   return hipGetLastError();
 }
 

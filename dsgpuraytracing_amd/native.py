@@ -104,6 +104,10 @@ class pt_film_info(ctypes.Structure):
                 ("accumulate_ms", c_double), ("resolve_ms", c_double)]
 
 
+class pt_denoise_params(ctypes.Structure):
+    _fields_ = [("iterations", c_int32), ("normal_squarings", c_int32), ("sigma_l", c_float), ("sigma_p", c_float)]
+
+
 PT_FILM_LUM_FLOOR = 1e-3  # floor of the film's relative error (include/ptgpu.h), as a float32 in the arithmetic
 
 # Every symbol include/ptgpu.h and include/ptgpu_scene.h declare, with ctypes signatures.
@@ -140,6 +144,14 @@ _SIGS = {
     "pt_film_tile_error": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p]),
     "pt_film_get_info": (c_int32, [c_void_p, POINTER(pt_film_info)]),
     "pt_film_set_next_sample": (c_int32, [c_void_p, c_uint32]),
+    "pt_render_features_device": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p, c_void_p]),
+    "pt_render_features": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p]),
+    "pt_denoise_params_default": (c_int32, [POINTER(pt_denoise_params)]),
+    "pt_denoise_device": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(pt_denoise_params), c_void_p,
+                                    c_void_p]),
+    "pt_film_set_features": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p]),
+    "pt_film_denoise_device": (c_int32, [c_void_p, POINTER(pt_denoise_params), c_void_p, c_void_p, c_void_p]),
+    "pt_film_denoise": (c_int32, [c_void_p, POINTER(pt_denoise_params), c_void_p, c_void_p]),
     "pt_env_search_check": (c_int64, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
     # include/ptgpu_scene.h (bound with full types in scene_loader.py)
     "pt_host_scene_load": (c_int32, [c_char_p, c_int32, c_int32, c_char_p, POINTER(c_void_p)]),

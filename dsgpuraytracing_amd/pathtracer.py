@@ -182,6 +182,39 @@ class Device:
                                      hit.ctypes.data, t.ctypes.data, prim.ctypes.data, anyh.ctypes.data))
         return hit, t, prim, anyh
 
+    def render_features(self, tiles=None) -> dict:
+        """First-hit feature buffers of `tiles` (the whole frame by default;
+        pt_render_features, waits): `normal` (H, W, 3) float32, `position`
+        (H, W, 3) float32, `depth` (H, W) float32 -- the ray parameter of the
+        hit --, `bsdf` (H, W) int32 (-1: miss) and `albedo` (H, W, 3) float32,
+        looked up from the scene's BSDF table (0 on a miss).  Pixels outside
+        the tiles hold the miss record.  `records` is the raw (2, H, W, 4)
+        float32 buffer as pt_denoise_device reads it."""
+        hw = getattr(self, "_frame", None)
+        if hw is None:
+            raise ValueError("render_features: set_params first")
+        h, w = hw
+        rec = np.zeros((2, h, w, 4), np.float32)
+        rec[0, :, :, 3] = np.int32(-1).view(np.float32)
+        keep, arr = self._tiles(tile_fifo(w, h) if tiles is None else tiles)
+        check(self._lib.pt_render_features(self.handle, arr, len(keep), rec.ctypes.data))
+        bsdf = rec[0, :, :, 3].view(np.int32).copy()
+        albedo = np.zeros((h, w, 3), np.float32)
+        sc = self._scene_keepalive
+        if sc is not None:
+            table = np.array([list(b.albedo) for b in sc.arrays.bsdfs], np.float32).reshape(-1, 3)
+            hit = bsdf >= 0
+            albedo[hit] = table[bsdf[hit]]
+        return {"normal": rec[0, :, :, :3].copy(), "position": rec[1, :, :, :3].copy(), "depth": rec[1, :, :, 3].copy(),
+                "bsdf": bsdf, "albedo": albedo, "records": rec}
+
+    def render_features_device(self, tiles, feat_ptr: int, stream: int = 0):
+        """pt_render_features_device: the feature records of `tiles` into the
+        device buffer at feat_ptr (2 * W * H records of 16 B); queued on `stream`."""
+        keep, arr = self._tiles(tiles)
+        check(self._lib.pt_render_features_device(self.handle, arr, len(keep), ctypes.c_void_p(feat_ptr or None),
+                                                  ctypes.c_void_p(stream or None)))
+
     def stats(self) -> dict:
         s = native.pt_stats()
         check(self._lib.pt_get_stats(self.handle, ctypes.byref(s)))
@@ -288,6 +321,35 @@ class Film:
         check(self._lib.pt_film_tile_error(self.handle, arr, len(keep), out.ctypes.data))
         return out
 
+    def set_features(self, tiles=None, stream: int = 0):
+        """Render the first-hit feature records of `tiles` (the whole frame by
+        default) with the context's current camera (pt_film_set_features);
+        clear() marks them absent again."""
+        keep, arr = Device._tiles(tile_fifo(self.width, self.height) if tiles is None else tiles)
+        check(self._lib.pt_film_set_features(self.handle, arr, len(keep), ctypes.c_void_p(stream or None)))
+
+    def denoise(self, params=None, hdr: bool = True, rgba: bool = True):
+        """(hdr (H, W, 3) float32, rgba (H, W, 4) uint8) of the film's mean
+        filtered by the edge-avoiding denoiser (pt_film_denoise; waits); the
+        film itself is unchanged.  params: a native.pt_denoise_params, a dict
+        of its fields over the defaults, or None for the defaults.  An output
+        switched off is None."""
+        h, w = self.height, self.width
+        o_hdr = np.empty((h, w, 3), np.float32) if hdr else None
+        o_rgba = np.empty((h, w), np.uint32) if rgba else None
+        p = denoise_params(params)
+        check(self._lib.pt_film_denoise(self.handle, None if p is None else ctypes.byref(p),
+                                        *[None if a is None else a.ctypes.data for a in (o_hdr, o_rgba)]))
+        return o_hdr, None if o_rgba is None else o_rgba.view(np.uint8).reshape(h, w, 4)
+
+    def denoise_device(self, hdr_ptr: int = 0, rgba_ptr: int = 0, params=None, stream: int = 0):
+        """pt_film_denoise_device: device pointers (0 = not wanted) of W*H*3
+        float32 and W*H uint32; queued on `stream`."""
+        p = denoise_params(params)
+        check(self._lib.pt_film_denoise_device(self.handle, None if p is None else ctypes.byref(p),
+                                               ctypes.c_void_p(hdr_ptr or None), ctypes.c_void_p(rgba_ptr or None),
+                                               ctypes.c_void_p(stream or None)))
+
     def set_next_sample(self, next_sample: int):
         """The sample index the next pass starts at (pt_film_set_next_sample)."""
         check(self._lib.pt_film_set_next_sample(self.handle, int(next_sample)))
@@ -305,6 +367,31 @@ def to_color_device(dev: Device, hdr_ptr: int, w: int, h: int, rgba_ptr: int, re
     x0, y0, x1, y1 = (0, 0, w, h) if rect is None else (int(v) for v in rect)
     check(dev._lib.pt_to_color_device(dev.handle, ctypes.c_void_p(hdr_ptr or None), int(w), int(h), x0, y0, x1, y1,
                                       ctypes.c_void_p(rgba_ptr or None), ctypes.c_void_p(stream or None)))
+
+
+def denoise_params(params=None):
+    """None (the library's defaults), a native.pt_denoise_params, or a dict of
+    its fields laid over pt_denoise_params_default."""
+    if params is None or isinstance(params, native.pt_denoise_params):
+        return params
+    p = native.pt_denoise_params()
+    check(lib().pt_denoise_params_default(ctypes.byref(p)))
+    for k, v in dict(params).items():
+        if k not in ("iterations", "normal_squarings", "sigma_l", "sigma_p"):
+            raise ValueError(f"denoise_params: no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def denoise_device(dev: Device, cv_ptr: int, feat_ptr: int, w: int, h: int, out_ptr: int, params=None, stream: int = 0):
+    """pt_denoise_device: the filter on device buffers -- cv_ptr ((h, w, 4)
+    float32: colour and the variance of the mean luminance) and feat_ptr (a
+    feature buffer, 2 * w * h records) into out_ptr ((h, w, 4) float32, not
+    overlapping cv_ptr); queued on `stream`."""
+    p = denoise_params(params)
+    check(dev._lib.pt_denoise_device(dev.handle, ctypes.c_void_p(cv_ptr or None), ctypes.c_void_p(feat_ptr or None),
+                                     int(w), int(h), None if p is None else ctypes.byref(p),
+                                     ctypes.c_void_p(out_ptr or None), ctypes.c_void_p(stream or None)))
 
 
 class Scene:
@@ -530,7 +617,7 @@ class PathTracer:
         self.render_tiles(tile_fifo(w, h), stats=stats)
         self.state = State.DONE
 
-    def render_progressive(self, passes: int, target_error: Optional[float] = None):
+    def render_progressive(self, passes: int, target_error: Optional[float] = None, denoise=False):
         """Progressive rendering on a device film: up to `passes` passes of
         ns_aa fresh samples each over the tiles still active, accumulated on
         the GPU.  With a target, after every pass from the second on a tile
@@ -538,7 +625,10 @@ class PathTracer:
         its pixels' mean luminance) is <= target_error leaves the active set;
         it stops when the set is empty.  sampleBuffer / frameBuffer come from
         the film's resolve; self.last_progressive records the tiles, the
-        passes each one received and its final error."""
+        passes each one received and its final error.  denoise (True, or the
+        parameters Film.denoise takes): the film's first-hit features are set
+        once, before the passes, and sampleBuffer / frameBuffer hold the
+        denoised mean (Film.denoise) instead of the resolved one."""
         if not self.has_valid_configuration():
             raise RuntimeError("PathTracer is not configured (scene, camera, frame size)")
         h, w = self.sampleBuffer.shape[:2]
@@ -549,6 +639,8 @@ class PathTracer:
         active = list(range(len(tiles)))
         film = dev.film(w, h)
         try:
+            if denoise:
+                film.set_features(tiles)
             for p in range(int(passes)):
                 if not active:
                     break
@@ -557,7 +649,10 @@ class PathTracer:
                 if target_error is not None and p >= 1:
                     e = film.tile_error([tiles[i] for i in active])
                     active = [i for i, v in zip(active, e) if not v <= target_error]
-            hdr, rgba, _ = film.resolve(err=False)
+            if denoise:
+                hdr, rgba = film.denoise(None if denoise is True else denoise)
+            else:
+                hdr, rgba, _ = film.resolve(err=False)
             errors = film.tile_error(tiles)
             info = film.info()
         finally:

@@ -45,6 +45,10 @@
  *   pt_film_*                   no counterpart: a device-resident progressive film (accumulated
  *                               passes, per-pixel error, GPU resolve to HDR / RGBA8 / error) for
  *                               the display loop that redraws frameBuffer (application.cpp:142-160)
+ *   pt_render_features*         no counterpart: the camera ray's Intersection (trace_ray,
+ *                               pathtracer.cpp:435-456) kept per pixel: normal, hit point, depth, BSDF
+ *   pt_denoise_* / pt_film_denoise*   no counterpart: an edge-avoiding filter of the film's mean,
+ *                               guided by those records and the film's variance
  *
  * Conventions: plain C types and host pointers only; the caller owns every host
  * input and output; the library owns device memory until pt_destroy.  Calls on
@@ -437,6 +441,120 @@ int pt_film_get_info(pt_film* film, pt_film_info* out);
 /* Sets the sample index the next pass starts at (a film that continues an
  * earlier render, or one rank's share of a sample split).  Host state only. */
 int pt_film_set_next_sample(pt_film* film, uint32_t next_sample);
+
+/* ---- First-hit feature buffers (no reference counterpart: the reference's
+ * Intersection of the camera ray, trace_ray pathtracer.cpp:435-456, never
+ * leaves trace_ray).  A feature buffer of a W x H frame is two planes of 16-B
+ * records in one allocation of 2*W*H*16 bytes, laid out as the film: pixel
+ * p = x + y*W, y = 0 the bottom row:
+ *   feat[p]       = {N.x, N.y, N.z, bsdf}   f32 f32 f32 i32   unit shading normal, BSDF index
+ *   feat[W*H + p] = {P.x, P.y, P.z, z}      f32 x4            hit point, ray parameter t of the hit
+ * of the nearest hit of the ray pt_render_tiles traces through the pixel's
+ * CENTRE (its jitter replaced by 0.5, 0.5; the origin on the screen plane, the
+ * direction normalised, so z is a distance from the screen plane's point).  P
+ * is rebuilt from the primitive as the renderer's hit point is (barycentrics /
+ * sphere reprojection); N is the interpolated vertex normal, flipped to face
+ * the ray on a triangle and outward on a sphere, normalised (the zero vector
+ * if it has no length).  A miss writes {0, 0, 0, -1} and {0, 0, 0, 0}.
+ * The records describe the FIRST hit only: on a mirror or glass surface they
+ * are the mirror's or the glass's own, not those of what is seen in or
+ * through it.
+ *
+ * Frame size, scene and camera are the context's (PT_E_NOSCENE before
+ * pt_upload_scene / pt_set_camera / pt_set_params); tiles are clipped to the
+ * frame and only records of pixels inside them are written.  Stream semantics
+ * are pt_render_tiles_device's; the kernel runs on `stream` itself. */
+int pt_render_features_device(pt_ctx* ctx, const pt_tile* tiles, int32_t n_tiles, void* feat_dev, void* stream);
+/* The same into a host buffer of 2*width*height*16 bytes; waits. */
+int pt_render_features(pt_ctx* ctx, const pt_tile* tiles, int32_t n_tiles, void* feat_host);
+
+/* ---- Denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010)
+ * guided by the feature records and, as the spatial pass of SVGF, by the
+ * variance of the pixel's mean luminance, which the film already keeps.  No
+ * reference counterpart.  Like the film's, the arithmetic is a definition:
+ * every operator below is one separately rounded IEEE f32 operation, in the
+ * order written, nothing fused, `/` and sqrtf correctly rounded, no
+ * transcendental.
+ *
+ * Working record per pixel: cv[p] = {r, g, b, v}, 16 B; v is the variance of
+ * the mean luminance, v == +inf means unknown (fewer than two passes), and
+ * !(v >= 0) marks an invalid pixel (never rendered, or NaN): it is never used
+ * as a tap and comes out as {0, 0, 0, -1}.
+ *
+ * Iteration i = 0 .. iterations-1 reads one cv buffer and writes another with
+ * step s = 1 << i.  For a valid centre p with records c_p = cv[p].rgb,
+ * v_p = cv[p].v, N_p, bsdf_p, P_p, z_p (a centre whose colour is not finite is
+ * copied through unchanged), and L(c) = (0.2126f*c.r + 0.7152f*c.g) + 0.0722f*c.b:
+ *
+ * Variance prefilter, only when v_p is finite: 3x3 taps at distance 1
+ * whatever s is, dy = -1..1 outer, dx = -1..1 inner; a tap counts if it is in
+ * the frame, valid and its v finite; weights g = 1/4 centre, 1/8 edge, 1/16
+ * corner; sums start at 0 and a tap adds sv = sv + g*v, sg = sg + g;
+ *   vf = sv / sg;  sd = sqrtf(vf);  den = sigma_l*sd + 1e-6f
+ *
+ * Taps: dy = -2..2 outer, dx = -2..2 inner, q = p + s*(dx, dy),
+ * k[0] = 0.375f, k[1] = 0.25f, k[2] = 0.0625f, h = k[|dx|]*k[|dy|].  q is
+ * skipped when it is outside the frame, invalid, any channel of c_q is not
+ * finite, or bsdf_q != bsdf_p (which also separates hit from miss, and the
+ * emitter quad from the coplanar ceiling).  The centre tap has w = h.  Otherwise
+ *   bsdf_p >= 0:  c   = fmaxf(0, (N_p.x*N_q.x + N_p.y*N_q.y) + N_p.z*N_q.z)
+ *                 c   = c*c, normal_squarings times;  w_n = c
+ *                 d   = P_q - P_p
+ *                 x_p = fabsf((N_p.x*d.x + N_p.y*d.y) + N_p.z*d.z) / (sigma_p * z_p)
+ *                 w_p = fmaxf(0, 1 - x_p)
+ *   bsdf_p <  0:  w_n = w_p = 1
+ *   x_l = fabsf(L(c_q) - L(c_p)) / den;  w_l = 1 / (1 + x_l*x_l)    (w_l = 1 when v_p is +inf)
+ *   w   = ((h*w_n)*w_p)*w_l
+ *   vq  = v_q == +inf ? v_p : v_q
+ *   sum_c = sum_c + w*c_q (c = r, g, b);  sum_w = sum_w + w;  sum_v = sum_v + (w*w)*vq
+ * (sums start at 0; a skipped tap leaves them untouched).  Output:
+ *   out.rgb = sum_c / sum_w;   out.v = v_p == +inf ? +inf : sum_v / (sum_w*sum_w)
+ *
+ * Limitation: the guides are first-hit features.  On mirror and glass
+ * surfaces they are constant where the reflected or refracted image has
+ * edges, so only the luminance weight keeps those edges, and the filter gains
+ * less there (measured: DESIGN.md). */
+typedef struct pt_denoise_params {
+  int32_t iterations;        /* 1 .. 6 */
+  int32_t normal_squarings;  /* 0 .. 10: the normal weight is cos^(2^normal_squarings) */
+  float sigma_l;             /* > 0: luminance differences are measured in sigma_l standard deviations */
+  float sigma_p;             /* > 0: plane distances are measured in sigma_p * z_p */
+} pt_denoise_params;
+#define PT_DENOISE_SIGMA_P 0.05f
+/* iterations 5, normal_squarings 7 (sigma_n = 128), sigma_l 4 (SVGF's), sigma_p PT_DENOISE_SIGMA_P
+ * (the best of 0.005, 0.01, 0.02, 0.05 on the quality test's scenes: DESIGN.md). */
+int pt_denoise_params_default(pt_denoise_params* out);
+/* The filter on caller buffers: cv_dev (width*height*4 float) and feat_dev (a
+ * feature buffer) in, out_cv_dev (width*height*4 float) out; input and output
+ * must not overlap.  params NULL: the defaults; out-of-range values, or
+ * sigma_l / sigma_p not > 0: PT_E_INVALID.  The iterations' ping-pong
+ * buffers belong to the context (grown on demand, freed by pt_destroy).
+ * Queued on `stream` (NULL = the context's stream); returns without waiting. */
+int pt_denoise_device(pt_ctx* ctx, const float* cv_dev, const void* feat_dev, int32_t width, int32_t height,
+                      const pt_denoise_params* params, float* out_cv_dev, void* stream);
+
+/* ---- The film, denoised.  The film lazily owns a feature buffer and two cv
+ * buffers.  pt_film_set_features renders the feature records of the listed
+ * tiles with the context's current camera (the params' frame must be the
+ * film's: PT_E_INVALID otherwise); a pixel never covered keeps the miss
+ * record.  pt_film_clear marks the features absent again (a display loop
+ * clears when the camera moves).
+ * pt_film_denoise_device: the film's records -> cv (prepare), the iterations,
+ * then hdr_dev (W*H*3 float) and rgba_dev (W*H uint32, pt_to_color of hdr),
+ * either of which may be NULL; the film's records are not changed.  Prepare:
+ *   n == 0:  {0, 0, 0, -1}
+ *   rgb = sum / (float)n
+ *   v   = k >= 2 ? (fmaxf(M2, 0) / (float)n) / (float)(k - 1) : +inf
+ * (the quantity under the film error's square root).  An invalid pixel comes
+ * out as rgb 0, rgba 0xFF000000, as the resolve gives for a pixel never
+ * rendered.  PT_E_INVALID: no features set since creation / the last clear,
+ * the params' frame differs from the film's, bad parameters (NULL = the
+ * defaults).  Stream semantics and ordering as the other film calls. */
+int pt_film_set_features(pt_film* film, const pt_tile* tiles, int32_t n_tiles, void* stream);
+int pt_film_denoise_device(pt_film* film, const pt_denoise_params* params, float* hdr_dev, uint32_t* rgba_dev,
+                           void* stream);
+/* The same into host buffers; waits.  A display loop passes only rgba_host. */
+int pt_film_denoise(pt_film* film, const pt_denoise_params* params, float* hdr_host, uint32_t* rgba_host);
 
 /* Diagnostics for pt_to_color's tabulated codes: the number of float bit patterns in
  * [lo_bits, hi_bits) whose tabulated 8-bit code differs from the direct evaluation
