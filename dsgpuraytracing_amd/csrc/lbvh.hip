@@ -31,6 +31,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
@@ -696,15 +697,31 @@ extern "C" hipError_t ptk_build_lbvh(const LbvhIn* in, LbvhOut* out, hipStream_t
   LB_CHK(hipMalloc(&out->prim_map, (size_t)n * 4));
   LB_CHK(hipMalloc(&out->nodes4, (size_t)(ni + 1) * sizeof(DNode)));
   LB_CHK(hipMalloc(&out->nodes2, ni * sizeof(DNode2)));
-  if (n <= kLeafNumber) {  // a single leaf: one BVH4 node, one child, as the host path
+  // A single leaf (one BVH4 node, one child, as the host path): one primitive,
+  // or as many as both the reference's LEAF_NUMBER and the leaf limit allow.
+  if (n == 1 || n <= std::min(kLeafNumber, P.max_leaf)) {
     hipLaunchKernelGGL(k_identity, dim3(gn), dim3(B), 0, s, P);  // final order = sorted order
     LB_CHK(hipGetLastError());
     hipLaunchKernelGGL(k_gather, dim3(gn), dim3(B), 0, s, P, in->norms, out->prims, out->norms, out->prim_map);
     LB_CHK(hipGetLastError());
+    // The leaf's box from the float primitives the kernel tests, widened as
+    // prim_box widens them.  (scene_min + scene_extent, rounded to nearest,
+    // can fall below the largest float vertex: a box that misses its leaf.)
+    DPrim hp[kLeafNumber];
+    LB_CHK(hipMemcpyAsync(hp, in->prims, (size_t)n * sizeof(DPrim), hipMemcpyDeviceToHost, s));
+    LB_CHK(hipStreamSynchronize(s));
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = in->scene_min[k];
-      hi[k] = in->scene_min[k] + in->scene_extent[k];
+    for (int i = 0; i < n; ++i) {
+      const float v0[3] = {hp[i].v0.x, hp[i].v0.y, hp[i].v0.z};
+      const float e1[3] = {hp[i].e1.x, hp[i].e1.y, hp[i].e1.z}, e2[3] = {hp[i].e2.x, hp[i].e2.y, hp[i].e2.z};
+      int meta;
+      std::memcpy(&meta, &hp[i].v0.w, 4);
+      for (int k = 0; k < 3; ++k) {
+        const float a = (meta & 1) ? v0[k] + std::min(std::min(0.0f, e1[k]), e2[k]) : v0[k] - hp[i].e1.x;
+        const float b = (meta & 1) ? v0[k] + std::max(std::max(0.0f, e1[k]), e2[k]) : v0[k] + hp[i].e1.x;
+        lo[k] = std::min(lo[k], std::nextafter(a, -INFINITY));
+        hi[k] = std::max(hi[k], std::nextafter(b, INFINITY));
+      }
     }
     DNode d{};
     float inf = INFINITY;
@@ -725,7 +742,7 @@ extern "C" hipError_t ptk_build_lbvh(const LbvhIn* in, LbvhOut* out, hipStream_t
     LB_CHK(hipStreamSynchronize(s));
     out->n4 = 1;
     out->n2 = 1;
-    out->max_stack = 1;
+    out->max_stack = 0;  // one used slot: nothing is pushed beneath the leaf
     for (int k = 0; k < 3; ++k) {
       out->root_lo[k] = lo[k];
       out->root_hi[k] = hi[k];

@@ -283,6 +283,7 @@ struct pt_ctx {
   int n_lights = 0, n_bsdfs = 0;
   int bvh_stack = 0;  // worst-case traversal stack entries of the uploaded BVH
   size_t n_render_nodes = 0;
+  size_t n_nodes2 = 0;  // binary nodes in nodes2 (pt_debug_bvh_info)
   int64_t n_prims = 0;
   bool tri_only = false;  // every primitive a triangle
   float root_lo[3] = {0, 0, 0}, root_hi[3] = {0, 0, 0};
@@ -549,6 +550,62 @@ static int build_host_bvh(const pt_scene* s, std::vector<DNode>& dn, std::vector
     }
   }
   if ((int64_t)b2.size() >= ((int64_t)1 << 31)) return fail(PT_E_INVALID, "pt_upload_scene: too many BVH nodes");
+  // The binary nodes of the reference-count launch keep the caller's boxes:
+  // its visit counts model the reference's own traversal.
+  d2.resize(b2.size());
+  for (size_t i = 0; i < b2.size(); ++i) {
+    const B2& q = b2[i];
+    d2[i].a = make_float4(q.lo[0][0], q.hi[0][0], q.lo[0][1], q.hi[0][1]);
+    d2[i].b = make_float4(q.lo[1][0], q.hi[1][0], q.lo[1][1], q.hi[1][1]);
+    d2[i].c = make_float4(q.lo[0][2], q.hi[0][2], q.lo[1][2], q.hi[1][2]);
+    d2[i].e = make_int4(q.ref[0], q.ref[1], 0, 0);
+  }
+  // The render tree: the kernel tests the float primitives (v0, v0 + e1,
+  // v0 + e2; c -+ r), whose roundings can leave the caller's double boxes by a
+  // few ulps (v0 and e1 are rounded apart; their sum is not the rounded
+  // vertex).  Every child box is widened to what lies below it: a leaf's to
+  // its float primitives, an inner child's to that node's own child boxes
+  // (pre-order: children come later).
+  auto float_box = [&](int64_t first, int64_t count, float lo[3], float hi[3]) {
+    for (int64_t i = first; i < first + count; ++i) {
+      const double* g = s->prim_geom + 9 * i;
+      for (int k = 0; k < 3; ++k) {
+        double a, b;
+        const double v0 = (double)(float)g[k];
+        if (s->prim_type[i] == PT_PRIM_TRIANGLE) {
+          const double p2 = v0 + (double)(float)(g[3 + k] - g[k]), p3 = v0 + (double)(float)(g[6 + k] - g[k]);
+          a = std::min({v0, p2, p3});
+          b = std::max({v0, p2, p3});
+        } else {
+          const double r = std::fabs((double)(float)g[3]);
+          a = v0 - r;
+          b = v0 + r;
+        }
+        lo[k] = std::min(lo[k], round_down(a));
+        hi[k] = std::max(hi[k], round_up(b));
+      }
+    }
+  };
+  for (size_t i = b2.size(); i-- > 0;)
+    for (int side = 0; side < 2; ++side) {
+      B2& q = b2[i];
+      if (std::isinf(q.lo[side][0])) continue;  // the empty child of a one-leaf root
+      float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+      const int r = q.ref[side];
+      if (r < 0) {
+        float_box((int64_t)((~r) >> 3), (int64_t)(((~r) & 7) + 1), lo, hi);
+      } else {
+        for (int s2 = 0; s2 < 2; ++s2)
+          for (int k = 0; k < 3; ++k) {
+            lo[k] = std::min(lo[k], b2[(size_t)r].lo[s2][k]);
+            hi[k] = std::max(hi[k], b2[(size_t)r].hi[s2][k]);
+          }
+      }
+      for (int k = 0; k < 3; ++k) {
+        q.lo[side][k] = std::min(q.lo[side][k], lo[k]);
+        q.hi[side][k] = std::max(q.hi[side][k], hi[k]);
+      }
+    }
 
   // (2) collapse to 4-wide nodes: repeatedly open the internal child of the
   // largest surface area (the usual BVH2 -> BVH4 collapse).  Pre-order, so
@@ -760,14 +817,6 @@ static int build_host_bvh(const pt_scene* s, std::vector<DNode>& dn, std::vector
     return fail(PT_E_INVALID, "pt_upload_scene: BVH needs a deeper traversal stack (" + std::to_string(max_stack) +
                                   " > " + std::to_string(PT_STACK_MAX) + ")");
 
-  d2.resize(b2.size());
-  for (size_t i = 0; i < b2.size(); ++i) {
-    const B2& q = b2[i];
-    d2[i].a = make_float4(q.lo[0][0], q.hi[0][0], q.lo[0][1], q.hi[0][1]);
-    d2[i].b = make_float4(q.lo[1][0], q.hi[1][0], q.lo[1][1], q.hi[1][1]);
-    d2[i].c = make_float4(q.lo[0][2], q.hi[0][2], q.lo[1][2], q.hi[1][2]);
-    d2[i].e = make_int4(q.ref[0], q.ref[1], 0, 0);
-  }
   return PT_OK;
 }
 
@@ -802,6 +851,7 @@ static int build_gpu_bvh(pt_ctx* c, const pt_scene* s) {
   c->prim_map.adopt(out.prim_map, (size_t)in.n);
   c->nodes.adopt(out.nodes4, (size_t)out.n4);
   c->nodes2.adopt(out.nodes2, (size_t)std::max(1, out.n2));
+  c->n_nodes2 = (size_t)out.n2;
   c->n_render_nodes = (size_t)out.n4;
   if (out.max_stack > PT_STACK_MAX)
     return fail(PT_E_INVALID, "pt_upload_scene_lbvh: BVH needs a deeper traversal stack (" +
@@ -983,6 +1033,7 @@ static int upload_impl(pt_ctx* c, const pt_scene* s, bool gpu_bvh) {
     if (int rc = build_gpu_bvh(c, s0)) return rc;  // adopts prims/norms/prim_map/nodes in its own order
     HIPCHK(c->nodes2.reserve(d2.size()));
     HIPCHK(hipMemcpy(c->nodes2.p, d2.data(), d2.size() * sizeof(DNode2), hipMemcpyHostToDevice));
+    c->n_nodes2 = d2.size();
     c->bvh_stack = std::max(c->bvh_stack, ms0);
     if (c->bvh_stack > PT_STACK_MAX)
       return fail(PT_E_INVALID, "pt_upload_scene: BVH needs a deeper traversal stack (" +
@@ -1002,6 +1053,7 @@ static int upload_impl(pt_ctx* c, const pt_scene* s, bool gpu_bvh) {
     }
     HIPCHK(c->nodes2.reserve(d2.size()));
     HIPCHK(hipMemcpy(c->nodes2.p, d2.data(), d2.size() * sizeof(DNode2), hipMemcpyHostToDevice));
+    c->n_nodes2 = d2.size();
     HIPCHK(c->nodes.reserve(dn.size()));
     HIPCHK(hipMemcpy(c->nodes.p, dn.data(), dn.size() * sizeof(DNode), hipMemcpyHostToDevice));
     if (!perm.empty()) {
@@ -1017,6 +1069,18 @@ static int upload_impl(pt_ctx* c, const pt_scene* s, bool gpu_bvh) {
       c->root_hi[k] = round_up(N[0].bb_max[k]);
       c->root_lo_d[k] = N[0].bb_min[k];
       c->root_hi_d[k] = N[0].bb_max[k];
+    }
+    // ... and the root's child boxes, which build_host_bvh widened to the float primitives
+    for (int slot = 0; slot < 4 && !dn.empty(); ++slot) {
+      const float* lo[3] = {&dn[0].lox.x, &dn[0].loy.x, &dn[0].loz.x};
+      const float* hi[3] = {&dn[0].hix.x, &dn[0].hiy.x, &dn[0].hiz.x};
+      if (std::isinf(lo[0][slot])) continue;
+      for (int k = 0; k < 3; ++k) {
+        c->root_lo[k] = std::min(c->root_lo[k], lo[k][slot]);
+        c->root_hi[k] = std::max(c->root_hi[k], hi[k][slot]);
+        c->root_lo_d[k] = std::min(c->root_lo_d[k], (double)lo[k][slot]);
+        c->root_hi_d[k] = std::max(c->root_hi_d[k], (double)hi[k][slot]);
+      }
     }
   } else {
     int rc = build_gpu_bvh(c, s);
@@ -2233,7 +2297,13 @@ int pt_intersect(pt_ctx* c, int64_t n, const double* o, const double* d, const d
     f[(size_t)i] = (float)o[i];
     f[(size_t)(3 * n + i)] = (float)d[i];
   }
-  for (int64_t i = 0; i < n; ++i) f[(size_t)(6 * n + i)] = (float)max_t[i];
+  // The traversal's "not entered" mark is 3.0e38f and an unused BVH4 slot is a
+  // box at +inf: with max_t beyond the mark (the reference's default ray has
+  // +inf) a ray with no negative direction component enters the unused slots
+  // (tn = inf <= tf = inf) -- pushes the stack bound does not count and, in a
+  // host-built tree whose unused slots refer to node 0, a walk that never
+  // ends.  Render rays carry 3.0e38f; so do queries.
+  for (int64_t i = 0; i < n; ++i) f[(size_t)(6 * n + i)] = (float)std::min(max_t[i], 3.0e38);
   HIPCHK(c->q_f.reserve((size_t)n * 8));
   HIPCHK(c->q_i.reserve((size_t)n * 3));
   HIPCHK(hipMemcpyAsync(c->q_f.p, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
@@ -2259,6 +2329,36 @@ int pt_intersect(pt_ctx* c, int64_t n, const double* o, const double* d, const d
     if (any_hit) any_hit[i] = ib[(size_t)(2 * n + i)];
     if (t) t[i] = tb[(size_t)i];
   }
+  return PT_OK;
+}
+
+int pt_debug_bvh_info(pt_ctx* c, pt_bvh_info* out) {
+  if (!c || !out) return fail(PT_E_INVALID, "pt_debug_bvh_info: NULL argument");
+  if (!c->have_scene) return fail(PT_E_NOSCENE, "pt_debug_bvh_info before pt_upload_scene");
+  *out = pt_bvh_info{};
+  out->n_prims = c->n_prims;
+  out->n_nodes4 = (int64_t)c->n_render_nodes;
+  out->n_nodes2 = (int64_t)c->n_nodes2;
+  out->bvh_stack = c->bvh_stack;
+  out->has_prim_map = c->prim_map.p ? 1 : 0;
+  for (int k = 0; k < 3; ++k) {
+    out->root_lo[k] = c->root_lo[k];
+    out->root_hi[k] = c->root_hi[k];
+  }
+  return PT_OK;
+}
+
+int pt_debug_read_bvh(pt_ctx* c, void* nodes4, void* nodes2, void* prims, float* norms, int32_t* prim_map) {
+  if (!c) return fail(PT_E_INVALID, "NULL context");
+  if (!c->have_scene) return fail(PT_E_NOSCENE, "pt_debug_read_bvh before pt_upload_scene");
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  const size_t n = (size_t)c->n_prims;
+  if (nodes4) HIPCHK(hipMemcpy(nodes4, c->nodes.p, c->n_render_nodes * sizeof(DNode), hipMemcpyDeviceToHost));
+  if (nodes2 && c->n_nodes2) HIPCHK(hipMemcpy(nodes2, c->nodes2.p, c->n_nodes2 * sizeof(DNode2), hipMemcpyDeviceToHost));
+  if (prims) HIPCHK(hipMemcpy(prims, c->prims.p, n * sizeof(DPrim), hipMemcpyDeviceToHost));
+  if (norms) HIPCHK(hipMemcpy(norms, c->norms.p, n * 9 * sizeof(float), hipMemcpyDeviceToHost));
+  if (prim_map && c->prim_map.p) HIPCHK(hipMemcpy(prim_map, c->prim_map.p, n * sizeof(int32_t), hipMemcpyDeviceToHost));
   return PT_OK;
 }
 

@@ -108,7 +108,12 @@ class pt_denoise_params(ctypes.Structure):
     _fields_ = [("iterations", c_int32), ("normal_squarings", c_int32), ("sigma_l", c_float), ("sigma_p", c_float)]
 
 
-PT_FILM_LUM_FLOOR = 1e-3  # floor of the film's relative error (include/ptgpu.h), as a float32 in the arithmetic
+class pt_bvh_info(ctypes.Structure):
+    _fields_ = [("n_prims", c_int64), ("n_nodes4", c_int64), ("n_nodes2", c_int64), ("bvh_stack", c_int32),
+                ("has_prim_map", c_int32), ("root_lo", c_float * 3), ("root_hi", c_float * 3)]
+
+
+PT_FILM_LUM_FLOOR = 1e-3 # floor of the film's relative error (include/ptgpu.h), as a float32 in the arithmetic
 
 # Every symbol include/ptgpu.h and include/ptgpu_scene.h declare, with ctypes signatures.
 _SIGS = {
@@ -129,6 +134,8 @@ _SIGS = {
     "pt_get_stats": (c_int32, [c_void_p, POINTER(pt_stats)]),
     "pt_get_launch_times": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, POINTER(c_int32)]),
     "pt_get_wave_trace": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
+    "pt_debug_bvh_info": (c_int32, [c_void_p, POINTER(pt_bvh_info)]),
+    "pt_debug_read_bvh": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "pt_last_error": (c_char_p, []),
     "pt_to_color": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "pt_to_color_check": (c_int64, [c_uint32, c_uint32]),

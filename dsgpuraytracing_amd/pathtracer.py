@@ -182,6 +182,32 @@ class Device:
                                      hit.ctypes.data, t.ctypes.data, prim.ctypes.data, anyh.ctypes.data))
         return hit, t, prim, anyh
 
+    def read_bvh(self) -> dict:
+        """The render tree as it lies in device memory (pt_debug_bvh_info and
+        pt_debug_read_bvh; include/ptgpu.h has the byte layouts): `info` (the
+        pt_bvh_info fields, root_lo / root_hi as float32 arrays), `nodes4`
+        (n4, 32) float32 -- rows of lo.x, hi.x, lo.y, hi.y, lo.z, hi.z of the
+        four slots, then the four references, read them with
+        nodes4[:, 24:28].view(int32) --, `nodes2` (n2, 16) float32 likewise
+        (references in columns 12:14), `prims` (n, 12) float32, `norms` (n, 9)
+        float32 and `prim_map` (n,) int32, or None when the tree keeps the
+        caller's order."""
+        info = native.pt_bvh_info()
+        check(self._lib.pt_debug_bvh_info(self.handle, ctypes.byref(info)))
+        n = int(info.n_prims)
+        nodes4 = np.zeros((int(info.n_nodes4), 32), np.float32)
+        nodes2 = np.zeros((int(info.n_nodes2), 16), np.float32)
+        prims = np.zeros((n, 12), np.float32)
+        norms = np.zeros((n, 9), np.float32)
+        prim_map = np.zeros(n, np.int32) if info.has_prim_map else None
+        check(self._lib.pt_debug_read_bvh(self.handle, nodes4.ctypes.data, nodes2.ctypes.data if nodes2.size else None,
+                                          prims.ctypes.data, norms.ctypes.data,
+                                          None if prim_map is None else prim_map.ctypes.data))
+        d = {k: int(getattr(info, k)) for k in ("n_prims", "n_nodes4", "n_nodes2", "bvh_stack", "has_prim_map")}
+        d["root_lo"] = np.array(list(info.root_lo), np.float32)
+        d["root_hi"] = np.array(list(info.root_hi), np.float32)
+        return {"info": d, "nodes4": nodes4, "nodes2": nodes2, "prims": prims, "norms": norms, "prim_map": prim_map}
+
     def render_features(self, tiles=None) -> dict:
         """First-hit feature buffers of `tiles` (the whole frame by default;
         pt_render_features, waits): `normal` (H, W, 3) float32, `position`

@@ -318,7 +318,8 @@ int pt_render_frames_device(pt_ctx* ctx, const pt_tile* tiles, int32_t n_tiles, 
 int pt_tile_submit(pt_ctx* ctx, const pt_tile* tile, float* hdr_out_host, uint32_t* rgba_out_host);
 int pt_tile_finish(pt_ctx* ctx);
 /* Batched BVHAccel::intersect.  Rays: origin o[3n], direction d[3n] (normalised),
- * max_t[n] for the any-hit query.  Outputs (each nullable): nearest hit flag,
+ * max_t[n] for the any-hit query (clamped to 3.0e38, the traversal's "far":
+ * +inf, the reference's default, is welcome).  Outputs (each nullable): nearest hit flag,
  * t, primitive index (the caller's BVH order, whatever tree renders), and the any-hit
  * flag within (0, max_t). */
 int pt_intersect(pt_ctx* ctx, int64_t n, const double* o, const double* d, const double* max_t,
@@ -340,6 +341,43 @@ int pt_get_launch_times(pt_ctx* ctx, float* kernel_ms, float* resolve_ms, int32_
  * rounds it ran after it saw the queue drained.  out == NULL: only *n_waves
  * is set. */
 int pt_get_wave_trace(pt_ctx* ctx, int64_t* out, int64_t cap, int64_t* n_waves);
+/* Diagnostics (no reference counterpart): the render tree as it lies in
+ * device memory -- whichever is loaded: the GPU-built tree (the default and
+ * pt_upload_scene_lbvh), the host SAH tree (PT_BVH_BUILD=sah) or the caller's
+ * (=ref).  Read-only; no render path does any work for it.
+ * pt_debug_bvh_info: the sizes to allocate for pt_debug_read_bvh, the
+ * worst-case traversal stack the uploads computed and the root box.
+ * PT_E_NOSCENE before an upload, PT_E_INVALID for a NULL argument. */
+typedef struct pt_bvh_info {
+  int64_t n_prims;      /* primitives (and 9-float normal records, and prim_map entries) */
+  int64_t n_nodes4;     /* 4-wide nodes of the render tree */
+  int64_t n_nodes2;     /* binary nodes of the reference-count launch */
+  int32_t bvh_stack;    /* worst-case traversal stack entries (pt_stats.bvh_stack) */
+  int32_t has_prim_map; /* 1: the tree has its own primitive order and a map back to the caller's */
+  float root_lo[3], root_hi[3];
+} pt_bvh_info;
+int pt_debug_bvh_info(pt_ctx* ctx, pt_bvh_info* out);
+/* Copies the context's current buffers to host memory after waiting for the
+ * context's stream; any pointer may be NULL and is skipped (prim_map is also
+ * skipped when has_prim_map is 0).  Little-endian records:
+ *   nodes4: n_nodes4 x 128 B.  Six float[4] at byte 0, 16, .. 80: lo.x, hi.x,
+ *     lo.y, hi.y, lo.z, hi.z, element k of each belonging to child slot k;
+ *     int32[4] child references at byte 96; 16 B of padding.  A reference
+ *     >= 0 is a node index, < 0 a leaf cursor ~((first << 3) | (count - 1)):
+ *     primitives [first, first + count) of `prims`, count <= 8.  An unused
+ *     slot has all six planes at +inf.
+ *   nodes2: n_nodes2 x 64 B.  float[4] a = (c0.lo.x, c0.hi.x, c0.lo.y,
+ *     c0.hi.y), b = the same of child 1, c = (c0.lo.z, c0.hi.z, c1.lo.z,
+ *     c1.hi.z), int32[4] e = (c0 reference, c1 reference, 0, 0).  After
+ *     pt_upload_scene_lbvh its leaf cursors index `prims`; after
+ *     pt_upload_scene it is the caller's tree over the caller's order.
+ *   prims: n_prims x 48 B, three float[4].  Triangle: v0 = (p1, meta),
+ *     e1 = (p2 - p1, 0), e2 = (p3 - p1, 0); sphere: v0 = (centre, meta),
+ *     e1 = (r, r*r, 0, 0), e2 = 0.  meta is an int32 in a float's bits:
+ *     (bsdf << 1) | is_triangle.
+ *   norms: n_prims x 9 floats (the three vertex normals; 0 for spheres).
+ *   prim_map: n_prims int32, position in `prims` -> the caller's index. */
+int pt_debug_read_bvh(pt_ctx* ctx, void* nodes4, void* nodes2, void* prims, float* norms, int32_t* prim_map);
 const char* pt_last_error(void);
 
 /* Output row, host side (no device needed):

@@ -38,6 +38,9 @@ def test_invalid_arguments_return_codes():
     assert L.pt_get_stats(None, None) == native.PT_E_INVALID
     assert L.pt_create(0, None) == native.PT_E_INVALID
     assert L.pt_destroy(None) == native.PT_OK
+    info = native.pt_bvh_info()
+    assert L.pt_debug_bvh_info(None, ctypes.byref(info)) == native.PT_E_INVALID
+    assert L.pt_debug_read_bvh(None, None, None, None, None, None) == native.PT_E_INVALID
 
 
 def test_create_without_gpu_fails_cleanly():
@@ -58,6 +61,7 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(native.pt_bvh_node) == 6 * 8 + 4 * 8
     assert ctypes.sizeof(native.pt_params) == 28  # + sample_base
     assert ctypes.sizeof(native.pt_tile) == 16
+    assert ctypes.sizeof(native.pt_bvh_info) == 3 * 8 + 2 * 4 + 6 * 4
 
 
 def _fastdiv_init(d):
