@@ -30,6 +30,7 @@
 #include "launch_plan.h"
 #include "pt_device.h"
 #include "pt_error.h"
+#include "reproject.h"
 
 namespace {
 
@@ -309,6 +310,15 @@ struct pt_ctx {
   hipStream_t feat_stream = nullptr;
   bool feat_ordered = false;
   DevBuf<float4> dn_a, dn_b;  // pt_denoise_device: the iterations' ping-pong records (grown on demand)
+  // reprojection (pt_reproject_device, pt_film_reproject): the uploaded scene's
+  // BSDF types, and the keep table on the device with what it holds; a gather
+  // that comes on another stream than the last waits for the last one's event
+  std::vector<int32_t> bsdf_types;
+  DevBuf<uint32_t> rp_keep;
+  std::vector<uint32_t> rp_keep_host;
+  hipEvent_t ev_rp = nullptr;
+  hipStream_t rp_stream = nullptr;
+  bool rp_ordered = false;
 };
 
 // A progressive film (ptgpu.h: pt_film_*; kernels and record layout: film.h).
@@ -326,6 +336,15 @@ struct pt_film {
   DevBuf<float4> feat;   // 2 * W * H feature records (pt_film_set_features; allocated at first use)
   DevBuf<float4> cv[2];  // the denoiser's working records (allocated at first use)
   bool have_feat = false;  // set since creation / the last clear
+  pt_camera feat_cam{};    // the camera `feat` was rendered with
+  // pt_film_reproject: the second record and feature buffers it writes and then
+  // swaps with rec / feat (allocated at first use), the kept / reset counts of
+  // the last one and the events around its gather kernel
+  DevBuf<uint4> rec2;
+  DevBuf<float4> feat2;
+  DevBuf<unsigned long long> rp_counts;
+  hipEvent_t ev_rp[2] = {};
+  bool rp_timed = false;
   uint64_t next = 0;     // next sample index (<= 2^32)
   int64_t passes = 0;
   hipEvent_t ev_acc[2] = {}, ev_res[2] = {};  // around the last accumulate / resolve kernel
@@ -401,7 +420,9 @@ int pt_destroy(pt_ctx* c) {
   c->feat_out.release();
   c->dn_a.release();
   c->dn_b.release();
+  c->rp_keep.release();
   if (c->ev_feat) (void)hipEventDestroy(c->ev_feat);
+  if (c->ev_rp) (void)hipEventDestroy(c->ev_rp);
   c->nodes.release();
   c->nodes2.release();
   c->prim_map.release();
@@ -1106,6 +1127,8 @@ static int upload_impl(pt_ctx* c, const pt_scene* s, bool gpu_bvh) {
   }
   c->n_lights = (int)ls.size();
   c->n_bsdfs = (int)bs.size();
+  c->bsdf_types.resize(bs.size());
+  for (size_t i = 0; i < bs.size(); ++i) c->bsdf_types[i] = bs[i].type;
   c->n_prims = s->n_prims;
   c->tri_only = std::all_of(s->prim_type, s->prim_type + s->n_prims, [](int t) { return t == PT_PRIM_TRIANGLE; });
   c->have_scene = true;
@@ -1555,7 +1578,10 @@ static void film_free(pt_film* f) {
   f->feat.release();
   f->cv[0].release();
   f->cv[1].release();
-  for (hipEvent_t e : {f->ev_acc[0], f->ev_acc[1], f->ev_res[0], f->ev_res[1], f->ev_order})
+  f->rec2.release();
+  f->feat2.release();
+  f->rp_counts.release();
+  for (hipEvent_t e : {f->ev_acc[0], f->ev_acc[1], f->ev_res[0], f->ev_res[1], f->ev_order, f->ev_rp[0], f->ev_rp[1]})
     if (e) (void)hipEventDestroy(e);
   delete f;
 }
@@ -1995,6 +2021,7 @@ int pt_film_set_features(pt_film* f, const pt_tile* tiles, int32_t n_tiles, void
   if (!f->have_feat) HIPCHK(ptk_features_clear(f->feat.p, f->W, f->H, s));  // a pixel never covered: the miss record
   if ((rc = features_launch(c, tl, f->feat.p, s))) return rc;
   f->have_feat = true;
+  f->feat_cam = c->cam;
   return film_end(f, s);
 }
 
@@ -2048,6 +2075,144 @@ int pt_film_denoise(pt_film* f, const pt_denoise_params* params, float* hdr_host
   if (hdr_host) HIPCHK(hipMemcpyAsync(hdr_host, f->out_hdr.p, 3 * px * sizeof(float), hipMemcpyDeviceToHost, s));
   if (rgba_host) HIPCHK(hipMemcpyAsync(rgba_host, f->out_rgba.p, px * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  return PT_OK;
+}
+
+// ---- reprojection (ptgpu.h: pt_reproject_*, pt_film_reproject; kernel: reproject.hip; host parts: reproject_host.cpp)
+int pt_reproject_params_default(pt_reproject_params* out) {
+  if (!out) return fail(PT_E_INVALID, "pt_reproject_params_default: out is NULL");
+  reproject_params_default(out);
+  return PT_OK;
+}
+
+// The parameters a call runs with: the defaults for NULL, else the caller's, checked.
+static int reproject_params(const pt_reproject_params* in, pt_reproject_params* out, const char* fn) {
+  if (!in) return pt_reproject_params_default(out);
+  if (const char* what = reproject_params_error(*in)) return fail(PT_E_INVALID, std::string(fn) + ": " + what);
+  *out = *in;
+  return PT_OK;
+}
+
+static int reproject_camera_check(const pt_camera& cam, const char* fn) {
+  if (!reproject_orthonormal(cam))
+    return fail(PT_E_INVALID, std::string(fn) + ": the old camera's c2w is not orthonormal within 1e-9 (the projection "
+                                                "into it takes coordinates by dot products with its columns)");
+  return PT_OK;
+}
+
+// The gather of one frame on `s`: the keep table of `types` (uploaded when it
+// changed), the counts zeroed when wanted, the kernel, between ev[0] and ev[1]
+// when given.
+static int reproject_launch(pt_ctx* c, const pt_camera& old_cam, const uint4* rec, const float4* fo, const float4* fn,
+                            int W, int H, const int32_t* types, int n_types, const pt_reproject_params& prm, uint4* out,
+                            unsigned long long* counts, hipEvent_t* ev, hipStream_t s) {
+  std::vector<uint32_t> keep((size_t)n_types);
+  reproject_keep_table(types, n_types, keep.data());
+  if (!c->ev_rp) HIPCHK(hipEventCreateWithFlags(&c->ev_rp, hipEventDisableTiming));
+  if (c->rp_ordered && c->rp_stream != s) HIPCHK(hipStreamWaitEvent(s, c->ev_rp, 0));
+  if (int rc = sync_list(c->rp_keep, c->rp_keep_host, keep.data(), keep.size(), s)) return rc;
+  ReprojectArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.rec = rec;
+  a.fo = fo;
+  a.fn = fn;
+  a.keep = c->rp_keep.p;
+  a.out = out;
+  a.counts = counts;
+  a.W = W;
+  a.H = H;
+  a.n_bsdfs = n_types;
+  reproject_camera(old_cam, &a.cam);
+  a.normal_cos_min = prm.normal_cos_min;
+  a.sigma_p = prm.sigma_p;
+  a.max_samples = prm.max_samples;
+  if (counts) HIPCHK(hipMemsetAsync(counts, 0, 2 * sizeof(unsigned long long), s));
+  if (ev) HIPCHK(hipEventRecord(ev[0], s));
+  HIPCHK(ptk_reproject(&a, s));
+  if (ev) HIPCHK(hipEventRecord(ev[1], s));
+  HIPCHK(hipEventRecord(c->ev_rp, s));
+  c->rp_stream = s;
+  c->rp_ordered = true;
+  return PT_OK;
+}
+
+int pt_reproject_device(pt_ctx* c, const pt_camera* old_cam, const void* rec_dev, const void* feat_old_dev,
+                        const void* feat_new_dev, int32_t width, int32_t height, const int32_t* bsdf_types_host,
+                        int32_t n_bsdfs, const pt_reproject_params* params, void* rec_out_dev, uint64_t* counts_dev,
+                        void* stream) {
+  // what needs no context first
+  pt_reproject_params prm;
+  if (int rc = reproject_params(params, &prm, "pt_reproject_device")) return rc;
+  if (!old_cam || !rec_dev || !feat_old_dev || !feat_new_dev || !rec_out_dev)
+    return fail(PT_E_INVALID, "pt_reproject_device: NULL argument");
+  if (width < 1 || height < 1 || width > 65535 || height > 65535 || (int64_t)width * height > (int64_t)1 << 30)
+    return fail(PT_E_INVALID, "pt_reproject_device: width and height must be 1 .. 65535 and width * height <= 2^30");
+  const size_t px = (size_t)width * (size_t)height;
+  const uintptr_t a0 = (uintptr_t)rec_dev, b0 = (uintptr_t)rec_out_dev, len = 2 * px * sizeof(uint4);
+  if (a0 < b0 + len && b0 < a0 + len)
+    return fail(PT_E_INVALID, "pt_reproject_device: input and output records overlap (the gather reads any pixel)");
+  if (int rc = reproject_camera_check(*old_cam, "pt_reproject_device")) return rc;
+  if (bsdf_types_host && n_bsdfs < 0) return fail(PT_E_INVALID, "pt_reproject_device: negative n_bsdfs");
+  if (!c) return fail(PT_E_INVALID, "pt_reproject_device: NULL context");
+  if (!bsdf_types_host) {
+    if (!c->have_scene) return fail(PT_E_NOSCENE, "pt_reproject_device: no BSDF types given and no scene uploaded");
+    bsdf_types_host = c->bsdf_types.data();
+    n_bsdfs = (int32_t)c->bsdf_types.size();
+  }
+  HIPCHK(hipSetDevice(c->device));
+  return reproject_launch(c, *old_cam, (const uint4*)rec_dev, (const float4*)feat_old_dev, (const float4*)feat_new_dev,
+                          width, height, bsdf_types_host, n_bsdfs, prm, (uint4*)rec_out_dev,
+                          (unsigned long long*)counts_dev, nullptr, stream ? (hipStream_t)stream : c->stream);
+}
+
+int pt_film_reproject(pt_film* f, const pt_reproject_params* params, void* stream) {
+  if (!f) return fail(PT_E_INVALID, "pt_film_reproject: NULL film");
+  pt_reproject_params prm;
+  int rc = reproject_params(params, &prm, "pt_film_reproject");
+  if (rc) return rc;
+  if (!f->have_feat)
+    return fail(PT_E_INVALID, "pt_film_reproject: no features (pt_film_set_features after creation / pt_film_clear)");
+  pt_ctx* c = f->ctx;
+  if ((rc = check_ready(c))) return rc;
+  if ((rc = film_frame_check(f, "pt_film_reproject"))) return rc;
+  if ((rc = reproject_camera_check(f->feat_cam, "pt_film_reproject"))) return rc;
+  if ((rc = tile_launch(c))) return rc;
+  HIPCHK(hipSetDevice(c->device));
+  const pt_tile whole = {0, 0, f->W, f->H};
+  std::vector<int4> tl;
+  if ((rc = build_tiles(c, &whole, 1, tl))) return rc;
+  const size_t px = (size_t)f->W * (size_t)f->H;
+  FILM_ALLOC(f->rec2.reserve(2 * px));
+  FILM_ALLOC(f->feat2.reserve(2 * px));
+  FILM_ALLOC(f->rp_counts.reserve(2));
+  for (hipEvent_t& e : f->ev_rp)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if ((rc = film_begin(f, s))) return rc;
+  if ((rc = features_launch(c, tl, f->feat2.p, s))) return rc;  // (the whole frame: every record is written)
+  if ((rc = reproject_launch(c, f->feat_cam, f->rec.p, f->feat.p, f->feat2.p, f->W, f->H, c->bsdf_types.data(),
+                             (int)c->bsdf_types.size(), prm, f->rec2.p, f->rp_counts.p, f->ev_rp, s)))
+    return rc;
+  f->rp_timed = true;
+  std::swap(f->rec, f->rec2);
+  std::swap(f->feat, f->feat2);
+  f->feat_cam = c->cam;
+  return film_end(f, s);
+}
+
+int pt_film_get_reproject_info(pt_film* f, pt_reproject_info* out) {
+  if (!f || !out) return fail(PT_E_INVALID, "pt_film_get_reproject_info: NULL argument");
+  std::memset(out, 0, sizeof(*out));
+  if (!f->rp_timed) return PT_OK;
+  HIPCHK(hipSetDevice(f->ctx->device));
+  HIPCHK(hipEventSynchronize(f->ev_rp[1]));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, f->ev_rp[0], f->ev_rp[1]));
+  unsigned long long n[2] = {0, 0};
+  HIPCHK(hipMemcpy(n, f->rp_counts.p, sizeof(n), hipMemcpyDeviceToHost));
+  out->kept = (int64_t)n[0];
+  out->reset = (int64_t)n[1];
+  out->reproject_ms = ms;
   return PT_OK;
 }
 

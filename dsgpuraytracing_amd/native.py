@@ -108,6 +108,14 @@ class pt_denoise_params(ctypes.Structure):
     _fields_ = [("iterations", c_int32), ("normal_squarings", c_int32), ("sigma_l", c_float), ("sigma_p", c_float)]
 
 
+class pt_reproject_params(ctypes.Structure):
+    _fields_ = [("normal_cos_min", c_float), ("sigma_p", c_float), ("max_samples", c_uint32)]
+
+
+class pt_reproject_info(ctypes.Structure):
+    _fields_ = [("kept", c_int64), ("reset", c_int64), ("reproject_ms", c_double)]
+
+
 class pt_bvh_info(ctypes.Structure):
     _fields_ = [("n_prims", c_int64), ("n_nodes4", c_int64), ("n_nodes2", c_int64), ("bvh_stack", c_int32),
                 ("has_prim_map", c_int32), ("root_lo", c_float * 3), ("root_hi", c_float * 3)]
@@ -159,6 +167,11 @@ _SIGS = {
     "pt_film_set_features": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p]),
     "pt_film_denoise_device": (c_int32, [c_void_p, POINTER(pt_denoise_params), c_void_p, c_void_p, c_void_p]),
     "pt_film_denoise": (c_int32, [c_void_p, POINTER(pt_denoise_params), c_void_p, c_void_p]),
+    "pt_reproject_params_default": (c_int32, [POINTER(pt_reproject_params)]),
+    "pt_reproject_device": (c_int32, [c_void_p, POINTER(pt_camera), c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                      c_void_p, c_int32, POINTER(pt_reproject_params), c_void_p, c_void_p, c_void_p]),
+    "pt_film_reproject": (c_int32, [c_void_p, POINTER(pt_reproject_params), c_void_p]),
+    "pt_film_get_reproject_info": (c_int32, [c_void_p, POINTER(pt_reproject_info)]),
     "pt_env_search_check": (c_int64, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
     # include/ptgpu_scene.h (bound with full types in scene_loader.py)
     "pt_host_scene_load": (c_int32, [c_char_p, c_int32, c_int32, c_char_p, POINTER(c_void_p)]),

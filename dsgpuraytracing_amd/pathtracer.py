@@ -376,6 +376,23 @@ class Film:
                                                ctypes.c_void_p(hdr_ptr or None), ctypes.c_void_p(rgba_ptr or None),
                                                ctypes.c_void_p(stream or None)))
 
+    def reproject(self, params=None, stream: int = 0):
+        """Keep the film across a camera move (pt_film_reproject): the context
+        already holds the NEW camera (Device.set_camera); every pixel takes
+        over the records of the old frame's pixel that saw the same diffuse or
+        emissive first hit, or is reset.  params: a native.pt_reproject_params,
+        a dict of its fields over the defaults, or None; returns once queued."""
+        p = reproject_params(params)
+        check(self._lib.pt_film_reproject(self.handle, None if p is None else ctypes.byref(p),
+                                          ctypes.c_void_p(stream or None)))
+
+    def reproject_info(self) -> dict:
+        """kept / reset pixel counts and the gather kernel's device time of the
+        last reproject (pt_film_get_reproject_info; waits)."""
+        i = native.pt_reproject_info()
+        check(self._lib.pt_film_get_reproject_info(self.handle, ctypes.byref(i)))
+        return {k: getattr(i, k) for k, _ in native.pt_reproject_info._fields_}
+
     def set_next_sample(self, next_sample: int):
         """The sample index the next pass starts at (pt_film_set_next_sample)."""
         check(self._lib.pt_film_set_next_sample(self.handle, int(next_sample)))
@@ -418,6 +435,38 @@ def denoise_device(dev: Device, cv_ptr: int, feat_ptr: int, w: int, h: int, out_
     check(dev._lib.pt_denoise_device(dev.handle, ctypes.c_void_p(cv_ptr or None), ctypes.c_void_p(feat_ptr or None),
                                      int(w), int(h), None if p is None else ctypes.byref(p),
                                      ctypes.c_void_p(out_ptr or None), ctypes.c_void_p(stream or None)))
+
+
+def reproject_params(params=None):
+    """None (the library's defaults), a native.pt_reproject_params, or a dict
+    of its fields laid over pt_reproject_params_default."""
+    if params is None or isinstance(params, native.pt_reproject_params):
+        return params
+    p = native.pt_reproject_params()
+    check(lib().pt_reproject_params_default(ctypes.byref(p)))
+    for k, v in dict(params).items():
+        if k not in ("normal_cos_min", "sigma_p", "max_samples"):
+            raise ValueError(f"reproject_params: no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def reproject_device(dev: Device, old_camera: native.pt_camera, rec_ptr: int, feat_old_ptr: int, feat_new_ptr: int,
+                     w: int, h: int, out_ptr: int, bsdf_types=None, params=None, counts_ptr: int = 0, stream: int = 0):
+    """pt_reproject_device: the reprojection gather on device buffers -- the
+    film records at rec_ptr ((2, h, w, 4) uint32) seen by old_camera with the
+    features at feat_old_ptr, through the new camera's features at
+    feat_new_ptr, into out_ptr (not overlapping rec_ptr).  bsdf_types: the
+    PT_BSDF_* type per BSDF index (None: the uploaded scene's); counts_ptr: two
+    uint64 on the device, overwritten with (kept, reset); queued on `stream`."""
+    p = reproject_params(params)
+    types = None if bsdf_types is None else np.ascontiguousarray(bsdf_types, dtype=np.int32)
+    check(dev._lib.pt_reproject_device(dev.handle, ctypes.byref(old_camera), ctypes.c_void_p(rec_ptr or None),
+                                       ctypes.c_void_p(feat_old_ptr or None), ctypes.c_void_p(feat_new_ptr or None),
+                                       int(w), int(h), None if types is None else types.ctypes.data,
+                                       0 if types is None else len(types), None if p is None else ctypes.byref(p),
+                                       ctypes.c_void_p(out_ptr or None), ctypes.c_void_p(counts_ptr or None),
+                                       ctypes.c_void_p(stream or None)))
 
 
 class Scene:
@@ -688,6 +737,52 @@ class PathTracer:
         self.last_stats = dev.stats()
         self.last_progressive = {"tiles": tiles, "passes": counts, "tile_error": errors,
                                  "spp": self.ns_aa, "total_passes": int(info["passes"])}
+
+    def render_interactive(self, cameras, passes_per_camera: int, denoise=False, reproject=True):
+        """A display loop over a camera path on ONE device film (a generator).
+        For each camera: set_camera; then the film's features are set (the
+        first camera), the film is reprojected into the new view
+        (Film.reproject: later cameras; reproject may be the parameters it
+        takes), or, with reproject=False, cleared and its features set again;
+        then passes_per_camera passes of ns_aa fresh samples; then
+        sampleBuffer / frameBuffer take the film's resolve, or with denoise
+        (True, or Film.denoise's parameters) its denoised mean.  Yields, per
+        camera, Film.reproject_info() of that camera's reproject (zeros where
+        none ran).  Sample indices go on across the whole path unless the film
+        is cleared."""
+        if self.scene is None or self.sampleBuffer.size == 0:
+            raise RuntimeError("PathTracer is not configured (scene, frame size)")
+        h, w = self.sampleBuffer.shape[:2]
+        dev = self._device()
+        tiles = tile_fifo(w, h)
+        none = {k: 0 for k, _ in native.pt_reproject_info._fields_}
+        film = None
+        try:
+            for i, cam in enumerate(cameras):
+                self.set_camera(cam)
+                self._params()
+                info = dict(none)
+                if film is None:
+                    film = dev.film(w, h)
+                    film.set_features(tiles)
+                elif reproject:
+                    film.reproject(None if reproject is True else reproject)
+                    info = film.reproject_info()
+                else:
+                    film.clear()
+                    film.set_features(tiles)
+                for _ in range(int(passes_per_camera)):
+                    film.add_pass(tiles)
+                if denoise:
+                    hdr, rgba = film.denoise(None if denoise is True else denoise)
+                else:
+                    hdr, rgba, _ = film.resolve(err=False)
+                self.sampleBuffer[...] = hdr
+                self.frameBuffer[...] = rgba
+                yield info
+        finally:
+            if film is not None:
+                film.close()
 
     def stop(self):
         if self.state in (State.RENDERING, State.DONE):

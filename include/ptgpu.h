@@ -49,6 +49,8 @@
  *                               pathtracer.cpp:435-456) kept per pixel: normal, hit point, depth, BSDF
  *   pt_denoise_* / pt_film_denoise*   no counterpart: an edge-avoiding filter of the film's mean,
  *                               guided by those records and the film's variance
+ *   pt_reproject_* / pt_film_reproject   no counterpart: the film kept across a camera move, its
+ *                               records gathered through the first hits of both cameras
  *
  * Conventions: plain C types and host pointers only; the caller owns every host
  * input and output; the library owns device memory until pt_destroy.  Calls on
@@ -575,8 +577,8 @@ int pt_denoise_device(pt_ctx* ctx, const float* cv_dev, const void* feat_dev, in
  * buffers.  pt_film_set_features renders the feature records of the listed
  * tiles with the context's current camera (the params' frame must be the
  * film's: PT_E_INVALID otherwise); a pixel never covered keeps the miss
- * record.  pt_film_clear marks the features absent again (a display loop
- * clears when the camera moves).
+ * record.  pt_film_clear marks the features absent again (when the camera
+ * moves a display loop clears, or keeps the film with pt_film_reproject below).
  * pt_film_denoise_device: the film's records -> cv (prepare), the iterations,
  * then hdr_dev (W*H*3 float) and rgba_dev (W*H uint32, pt_to_color of hdr),
  * either of which may be NULL; the film's records are not changed.  Prepare:
@@ -593,6 +595,101 @@ int pt_film_denoise_device(pt_film* film, const pt_denoise_params* params, float
                            void* stream);
 /* The same into host buffers; waits.  A display loop passes only rgba_host. */
 int pt_film_denoise(pt_film* film, const pt_denoise_params* params, float* hdr_host, uint32_t* rgba_host);
+
+/* ---- Reprojection: the film kept across a camera move (the temporal half of
+ * SVGF; the denoiser above is the spatial half).  No reference counterpart.
+ * Instead of pt_film_clear, every pixel of the NEW camera's frame looks up
+ * the pixel of the OLD camera's frame that saw the same surface point and
+ * takes over its records; a pixel whose point the old frame did not see, or
+ * whose radiance depends on the view, is reset.  Like the film's, the
+ * arithmetic is a definition: every operator below is one separately rounded
+ * IEEE f32 operation, in the order written, nothing fused, `/` correctly
+ * rounded.
+ *
+ * Inputs for a W x H frame: the old records rec (the film's two 16-B planes,
+ * {sum.r, sum.g, sum.b, n} and {mu, M2, k, pad}), the old feature buffer fo,
+ * the new feature buffer fn, the old camera as f32 -- pos, the columns c0, c1,
+ * c2 of c2w, ax = (float)(screen_w / screen_dist), ay likewise, each double
+ * rounded once, the values the feature pass traces with -- and keep[b] per
+ * BSDF index: 1 for PT_BSDF_DIFFUSE and PT_BSDF_EMISSION, 0 for mirror,
+ * refraction and glass, whose radiance depends on the view.
+ *
+ * New pixel p, {N_p, bsdf_p} = fn[p], {P_p, z_p} = fn[W*H + p], is RESET (both
+ * records all zero) unless every test passes; then it is KEPT:
+ *   bsdf_p >= 0 && bsdf_p < n_bsdfs && keep[bsdf_p]      (a miss is reset: without an environment
+ *                                                         light it converges in one pass, with one its
+ *                                                         radiance depends on the direction)
+ *   v  = P_p - pos
+ *   cx = (v.x*c0.x + v.y*c0.y) + v.z*c0.z;  cy, cz likewise with c1, c2
+ *   cz < 0                                                (in front of the old camera)
+ *   iz = 0 - cz
+ *   u  = ((cx / iz) / ax + 0.5f) * (float)W
+ *   w  = ((cy / iz) / ay + 0.5f) * (float)H
+ *   u >= 0 && u < (float)W && w >= 0 && w < (float)H      (a NaN fails)
+ *   q  = (int)u + (int)w * W                              (the nearest tap: Welford states do not
+ *                                                         interpolate, and one tap is bit-exact)
+ *   {N_q, bsdf_q} = fo[q], {P_q, z_q} = fo[W*H + q]
+ *   bsdf_q == bsdf_p
+ *   c = (N_p.x*N_q.x + N_p.y*N_q.y) + N_p.z*N_q.z;  c >= normal_cos_min
+ *   d = P_q - P_p
+ *   fabsf((N_p.x*d.x + N_p.y*d.y) + N_p.z*d.z) <= sigma_p * z_p     (occluders and disocclusions)
+ *   rec[q].n > 0
+ * A kept pixel takes q's two records bit for bit when max_samples == 0 or
+ * n <= max_samples; otherwise, with n' = max_samples:
+ *   f = (float)n' / (float)n;  sum'_c = sum_c * f;  mu' = mu;  M2' = M2 * f
+ *   k' = max(1, (uint32)(((uint64)k * n') / n));  n' replaces n, pad is kept
+ * so the per-pass variance M2 / n stays and the confidence shrinks: fresh
+ * passes outweigh the history sooner.
+ *
+ * Limitation: the old samples were shaded for the old view; for the kept BSDF
+ * types the first hit's outgoing radiance does not depend on it.  Geometry
+ * does not move between the two feature buffers. */
+typedef struct pt_reproject_params {
+  float normal_cos_min;  /* -1 .. 1: the least cosine between the two first hits' normals */
+  float sigma_p;         /* > 0: the plane distance allowed, in units of z_p */
+  uint32_t max_samples;  /* 0: no cap; else a kept pixel's n is cut to this many samples */
+} pt_reproject_params;
+#define PT_REPROJECT_NORMAL_COS_MIN 0.9f
+#define PT_REPROJECT_SIGMA_P 0.02f
+/* normal_cos_min PT_REPROJECT_NORMAL_COS_MIN, sigma_p PT_REPROJECT_SIGMA_P, max_samples 0.  The
+ * candidates {0.8, 0.9, 0.95} x {0.005, 0.01, 0.02, 0.05} all keep the same pixels on the quality
+ * test's scenes, where the BSDF index already separates the surfaces; the middle ones were taken
+ * (DESIGN.md has the table and the argument). */
+int pt_reproject_params_default(pt_reproject_params* out);
+/* The gather on caller buffers: rec_dev (2*W*H records), feat_old_dev and
+ * feat_new_dev (feature buffers) in, rec_out_dev (2*W*H records) out, which
+ * must not overlap rec_dev.  old_cam's c2w must be orthonormal within 1e-9
+ * (projection by dot products needs it).  bsdf_types_host: n_bsdfs PT_BSDF_*
+ * values, read before the call returns; NULL: the uploaded scene's BSDFs
+ * (PT_E_NOSCENE without one; n_bsdfs is ignored).  params NULL: the defaults;
+ * a NaN, normal_cos_min outside [-1, 1] or sigma_p not > 0: PT_E_INVALID.
+ * counts_dev (nullable): two uint64 on the device, overwritten with the kept
+ * and the reset pixels.  Queued on `stream` (NULL = the context's stream);
+ * returns without waiting. */
+int pt_reproject_device(pt_ctx* ctx, const pt_camera* old_cam, const void* rec_dev, const void* feat_old_dev,
+                        const void* feat_new_dev, int32_t width, int32_t height, const int32_t* bsdf_types_host,
+                        int32_t n_bsdfs, const pt_reproject_params* params, void* rec_out_dev, uint64_t* counts_dev,
+                        void* stream);
+/* The film across a camera move: the caller has called pt_set_camera with the
+ * NEW camera.  pt_film_set_features remembers the camera it rendered with;
+ * pt_film_reproject renders the whole frame's features with the context's
+ * current camera into a second feature buffer, gathers (records, features,
+ * remembered camera) into a second record buffer, then swaps both pairs and
+ * remembers the current camera (the second buffers are allocated at first use
+ * and freed with the film).  passes and next_sample are not touched: fresh
+ * passes keep drawing fresh sample indices.  PT_E_INVALID, film unchanged: no
+ * features set since creation / the last clear, the params' frame differs
+ * from the film's, the remembered camera's c2w is not orthonormal, bad
+ * parameters (NULL = the defaults).  Stream semantics and ordering as the
+ * other film calls. */
+int pt_film_reproject(pt_film* film, const pt_reproject_params* params, void* stream);
+typedef struct pt_reproject_info {
+  int64_t kept;         /* pixels of the last pt_film_reproject that took over records */
+  int64_t reset;        /* pixels it reset; kept + reset = width * height */
+  double reproject_ms;  /* device time of its gather kernel alone (hipEvent; 0: none yet) */
+} pt_reproject_info;
+/* Of the film's last pt_film_reproject (all zero before the first); waits for it. */
+int pt_film_get_reproject_info(pt_film* film, pt_reproject_info* out);
 
 /* Diagnostics for pt_to_color's tabulated codes: the number of float bit patterns in
  * [lo_bits, hi_bits) whose tabulated 8-bit code differs from the direct evaluation
