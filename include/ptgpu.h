@@ -87,8 +87,10 @@ extern "C" {
 #define PT_BSDF_EMISSION 4
 /* Light types follow SceneLight::getType(): Directional 0, Hemisphere 1, Point 2, Area 3;
  * Environment 4 (EnvironmentLight, src/static_scene/environment_light.cpp, whose own
- * getType() says 1) — its map is pt_scene.env_*; at most one, last in the list as
- * PathTracer::set_scene pushes it (src/pathtracer.cpp:88-90). */
+ * getType() says 1) — its map is pt_scene.env_*; at most one (pt_upload_scene refuses a
+ * second).  PathTracer::set_scene pushes it last (src/pathtracer.cpp:88-90), but its place
+ * is not checked: trace_ray samples the lights in list order whatever their kind, and so
+ * does the render kernel, so an environment light anywhere in the list is honoured. */
 #define PT_LIGHT_DIRECTIONAL 0
 #define PT_LIGHT_HEMISPHERE 1
 #define PT_LIGHT_POINT 2

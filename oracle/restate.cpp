@@ -600,7 +600,8 @@ struct Tracer {
         sR.max_t = dist_to_light * 0.999;
         st.shadow++;
         if (intersect(sR, nullptr)) {
-          RS_DBG("    shadow ray occluded (Li %.4g pdf %.4g dist %.6g)\n", light_L.r, pdf, dist_to_light);
+          RS_DBG("    shadow ray occluded (Li %.4g pdf %.4g dist %.6g) o=(%.9g %.9g %.9g) d=(%.9g %.9g %.9g)\n", light_L.r, pdf,
+                 dist_to_light, sR.o.x, sR.o.y, sR.o.z, sR.d.x, sR.d.y, sR.d.z);
           continue;
         }
         V3 w_in = w2o.mul(dir_to_light);

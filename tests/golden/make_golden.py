@@ -22,11 +22,15 @@ available on the GPU box) and stores inputs + outputs as small PTDUMP files:
                                at 128x128, 64 spp, two seeds (statistical parity)
   scene_hashes.json             sha256 of every array of the reference's flattened scene for the
                                bunny scenes and the C5 / c5big proxies with their map (1920x1080)
+  CBspheres_multilight.dae      CBspheres_lambertian.dae with four lights of four kinds (area, point,
+                               directional, ambient), coloured materials and a glass sphere of ior 1.2
+                               (multilight_dae below), its 64x64 scene dump and one reference render
+                               CBspheres_multilight_64x64{.scene,_s4_m4_l1_seed3.hdr}.ptd
   tocolor_in.ptd / tocolor_ref.ptd
                                HDR edge cases -> HDRImageBuffer::toColor's RGBA8
                                frameBuffer and save_image's flipped rows
 
-Usage: python tests/golden/make_golden.py [--only env|refraction|tocolor|baseline|c5big|c5hashes|highspp]
+Usage: python tests/golden/make_golden.py [--only env|refraction|tocolor|baseline|c5big|c5hashes|highspp|multilight]
 (needs oracle/_ref/ref_driver)
 """
 from __future__ import annotations
@@ -199,6 +203,94 @@ def make_highspp():
             ptdump.write(out, {"hdr": d["hdr"], "shape": d["shape"]})
 
 
+MULTILIGHT = "CBspheres_multilight"
+_EXTRA_LIGHTS = """
+    <light id="Point-light" name="PointLight">
+      <technique_common>
+        <point>
+          <color sid="color">1.2 0.4 0.2</color>
+          <constant_attenuation>1</constant_attenuation>
+          <linear_attenuation>0</linear_attenuation>
+          <quadratic_attenuation>0</quadratic_attenuation>
+        </point>
+      </technique_common>
+    </light>
+    <light id="Dir-light" name="DirLight">
+      <technique_common>
+        <directional>
+          <color sid="color">0.3 0.5 0.9</color>
+        </directional>
+      </technique_common>
+    </light>
+    <light id="Ambient-light" name="AmbientLight">
+      <technique_common>
+        <ambient>
+          <color sid="color">0.2 0.35 0.6</color>
+        </ambient>
+      </technique_common>
+    </light>"""
+_EXTRA_LIGHT_NODES = """
+      <node id="PointL" name="PointL" type="NODE">
+        <matrix sid="transform">1 0 0 0.55 0 1 0 -0.6 0 0 1 0.95 0 0 0 1</matrix>
+        <instance_light url="#Point-light"/>
+      </node>
+      <node id="DirL" name="DirL" type="NODE">
+        <matrix sid="transform">-0.8804769 0.2148353 0.4226183 0 0 0.8914323 -0.4531539 0 -0.4740891 -0.3989915 -0.7848855 0 0 0 0 1</matrix>
+        <instance_light url="#Dir-light"/>
+      </node>
+      <node id="AmbientL" name="AmbientL" type="NODE">
+        <matrix sid="transform">1 0 0 0 0 1 0 0 0 0 1 0 0 0 0 1</matrix>
+        <instance_light url="#Ambient-light"/>
+      </node>"""
+
+
+def multilight_dae(dst):
+    """assets/CBspheres_lambertian.dae with four lights of four kinds (its
+    area light recoloured, + a point, a directional and an ambient light),
+    coloured sphere, wall and floor materials and the second sphere's
+    commented-out glass material switched on with coloured reflectance /
+    transmittance and ior 1.2.  Everything else is the file as shipped."""
+    txt = open(C1).read()
+
+    def sub(old, new, count=1):
+        nonlocal txt
+        assert txt.count(old) >= 1, old
+        txt = txt.replace(old, new, count)
+
+    sub('<COLLADA', '<!-- Test fixture derived from the reference scene dae/sky/CBspheres_lambertian.dae: three lights\n'
+        '     added (point, directional, ambient), the area light and the materials coloured, the glass sphere\n'
+        '     switched on with ior 1.2 (tests/golden/make_golden.py multilight_dae). -->\n<COLLADA')
+    sub('<area>\n            <color sid="color">10 10 10</color>', '<area>\n            <color sid="color">6 1 0.2</color>')
+    sub('    </light>\n  </library_lights>', '    </light>' + _EXTRA_LIGHTS + '\n  </library_lights>')
+    g0 = txt.index('<effect id="glass-effect">')
+    c0 = txt.index('<!-- <extra>', g0)
+    c1 = txt.index('</extra> -->', c0) + len('</extra> -->')
+    glass = txt[c0:c1].replace('<!-- <extra>', '<extra>').replace('</extra> -->', '</extra>')
+    glass = glass.replace('<reflectance>1 1 1</reflectance>', '<reflectance>0.9 0.95 0.85</reflectance>')
+    glass = glass.replace('<transmittance>1 1 1</transmittance>', '<transmittance>0.8 0.9 0.7</transmittance>')
+    glass = glass.replace('<ior>1.45</ior>', '<ior>1.2</ior>')
+    assert '<ior>1.2</ior>' in glass and '0.8 0.9 0.7' in glass
+    txt = txt[:c0] + glass + txt[c1:]
+    sub('<color sid="diffuse">0.8 0.8 0.8 1</color>', '<color sid="diffuse">0.3 0.4 0.8 1</color>')        # lambertian sphere
+    f0 = txt.index('<effect id="floor-effect">')
+    txt = txt[:f0] + txt[f0:].replace('<color sid="diffuse">0.6 0.6 0.6 1</color>', '<color sid="diffuse">0.72 0.68 0.6 1</color>', 1)
+    sub('<instance_light url="#Area-light"/>\n      </node>', '<instance_light url="#Area-light"/>\n      </node>' + _EXTRA_LIGHT_NODES)
+    with open(dst, "w") as f:
+        f.write(txt)
+    return dst
+
+
+def make_multilight():
+    """tests/golden/CBspheres_multilight.dae, its 64x64 scene dump and one
+    64x64, 4 spp, -m 4 -l 1, -t 1 reference render (seed 3)."""
+    dae = multilight_dae(os.path.join(HERE, MULTILIGHT + ".dae"))
+    run([dae, "-w", "64", "-h", "64", "--mode", "dump", "--out", os.path.join(HERE, f"{MULTILIGHT}_64x64.scene.ptd")])
+    out = os.path.join(HERE, f"{MULTILIGHT}_64x64_s4_m4_l1_seed3.hdr.ptd")
+    run([dae, "-w", "64", "-h", "64", "-s", "4", "-m", "4", "-l", "1", "--seed", "3", "--out", out])
+    d = ptdump.read(out)
+    ptdump.write(out, {"hdr": d["hdr"], "shape": d["shape"]})
+
+
 def main():
     if not os.path.exists(REF):
         sys.exit("oracle/_ref/ref_driver missing: run `make -C oracle/ref` in the build container")
@@ -213,6 +305,8 @@ def main():
         return make_baseline_scenes()
     if only == "c5big":
         return make_baseline_scenes("c5bigproxy")
+    if only == "multilight":
+        return make_multilight()
     if only == "c5hashes":
         return make_hashes(c5_only=True)
     make_env()

@@ -31,7 +31,17 @@ def test_c1_scene_bit_identical_to_reference(fixture, w, h, cam):
 @pytest.mark.parametrize("name", ["CBspheres", "CBspheres_lambertian_pointlight", "CBspheres_lambertian_dirlight",
                                   "CBspheres_lambertian_ambientlight", "CBspheres_refraction"])
 def test_bsdf_and_light_variants_bit_identical(name):
-    got = scene_loader.load_dae(os.path.join(ROOT, "assets", name + ".dae"), 64, 64)
+    _variant_bit_identical(os.path.join(ROOT, "assets", name + ".dae"), name)
+
+
+def test_multilight_scene_bit_identical():
+    """Four lights of four kinds in one file, coloured glass of ior 1.2 (the
+    fixture the reference render of test_oracle.py's multilight case uses)."""
+    _variant_bit_identical(golden("CBspheres_multilight.dae"), "CBspheres_multilight")
+
+
+def _variant_bit_identical(dae, name):
+    got = scene_loader.load_dae(dae, 64, 64)
     ref = ptdump.read(golden(f"{name}_64x64.scene.ptd"))
     assert sorted(got) == sorted(ref)
     for k in ref:
