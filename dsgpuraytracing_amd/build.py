@@ -1,8 +1,10 @@
 """Builds the in-tree native library ``libptgpu.so`` for gfx950 with hipcc.
 
 The library holds the HIP kernels (csrc/pt_kernels.hip), the C ABI
-(csrc/pt_api.cpp, include/ptgpu.h) and the native host scene pipeline
-(csrc/scene_host.cpp).  It is built in-tree so that it travels with the
+(csrc/pt_api.cpp, include/ptgpu.h), the host flattening of an uploaded scene
+(csrc/scene_flatten.cpp) and the native host scene pipeline
+(csrc/scene_host.cpp).  Only pt_api.cpp and the .hip files are compiled as
+HIP; every other .cpp is plain C++.  It is built in-tree so that it travels with the
 repository snapshot to the GPU box; nothing is installed.
 """
 from __future__ import annotations
@@ -48,6 +50,11 @@ def hipcc() -> str:
     raise RuntimeError("hipcc not found: the HIP path cannot be built")
 
 
+def rocm_include() -> str:
+    """<rocm>/include, from where hipcc itself lies (<rocm>/bin/hipcc)."""
+    return os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc()))), "include")
+
+
 def build(force: bool = False, verbose: bool = False) -> str:
     if not force and up_to_date():
         return LIB
@@ -80,7 +87,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
             # with the round-3 follow-up rays; max-ILP neutral)
             cmd[1:1] = ["-mllvm", f"-amdgpu-sched-strategy={strategy}"]
         if src.endswith(".cpp") and "pt_api" not in src:
-            cmd.insert(1, "-xc++")  # host-only translation units
+            # host-only translation units; -xc++ drops hipcc's own ROCm include
+            # path, which pt_records.h needs for the vector types alone
+            cmd[1:1] = ["-xc++", "-D__HIP_PLATFORM_AMD__", f"-I{rocm_include()}"]
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
         objs.append(obj)
     for cmd, p in procs:

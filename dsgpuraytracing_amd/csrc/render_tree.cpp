@@ -1,6 +1,6 @@
 // render_tree.cpp -- the render tree pt_upload_scene builds over the handed-over
 // primitives (host only).  C ABI: pt_host_build_render_tree
-// (include/ptgpu_scene.h), called by pt_api.cpp's upload and by the CPU tests.
+// (include/ptgpu_scene.h), called by scene_flatten.cpp (the upload's host side) and by the CPU tests.
 #include <algorithm>
 #include <atomic>
 #include <cmath>

@@ -13,7 +13,7 @@ N_RAYS = 2048
 
 
 def device_prims(prim_type, prim_bsdf, geom, norm):
-    """pt_upload_scene's conversion (pt_api.cpp `convert`) of the caller's
+    """pt_upload_scene's conversion (scene_flatten.cpp `convert_prims`) of the caller's
     float64 primitives: (n, 12) float32 records and (n, 9) float32 normals."""
     g = np.asarray(geom, np.float64).reshape(-1, 9)
     t = np.asarray(prim_type).reshape(-1)
