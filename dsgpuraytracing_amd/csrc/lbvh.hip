@@ -35,6 +35,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "hip_owned.h"
 #include "pt_device.h"
 
 namespace lbvh {
@@ -653,34 +654,38 @@ extern "C" hipError_t ptk_build_lbvh(const LbvhIn* in, LbvhOut* out, hipStream_t
   P.max_leaf = 4;
   if (const char* e = std::getenv("PT_LBVH_CI")) P.ci = std::max(0.05f, std::min(8.0f, (float)std::atof(e)));  // tuning knobs
   if (const char* e = std::getenv("PT_LBVH_MAXLEAF")) P.max_leaf = std::max(1, std::min(kMaxLeaf, std::atoi(e)));
-  // scratch
-  uint32_t *keys_a = nullptr, *keys_b = nullptr;
-  int *ids_a = nullptr, *ids_b = nullptr, *ints = nullptr;
-  float *box = nullptr, *cost = nullptr, *dpc = nullptr;
-  int8_t* dpk = nullptr;
-  void* tmp = nullptr;
+  // scratch, and the outputs until the build has succeeded: freed at every return
+  DevBuf<uint32_t> keys_a, keys_b;
+  DevBuf<int> ids_a, ids_b, ints, o_map;
+  DevBuf<float> box, cost, dpc, o_norms;
+  DevBuf<int8_t> dpk;
+  DevBuf<char> tmp;
+  DevBuf<Item> fa, fb;
+  DevBuf<DPrim> o_prims;
+  DevBuf<DNode> o_nodes4;
+  DevBuf<DNode2> o_nodes2;
   size_t tmp_bytes = 0;
   const size_t ni = (size_t)(n > 1 ? n - 1 : 1);
-  LB_CHK(hipMalloc(&keys_a, (size_t)n * 4));
-  LB_CHK(hipMalloc(&keys_b, (size_t)n * 4));
-  LB_CHK(hipMalloc(&ids_a, (size_t)n * 4));
-  LB_CHK(hipMalloc(&ids_b, (size_t)n * 4));
+  LB_CHK(keys_a.reserve((size_t)n));
+  LB_CHK(keys_b.reserve((size_t)n));
+  LB_CHK(ids_a.reserve((size_t)n));
+  LB_CHK(ids_b.reserve((size_t)n));
   // child 2ni, parent ni+n, start ni, range ni, collapsed ni, flag ni, pos n, counters 4
-  LB_CHK(hipMalloc(&ints, (ni * 2 + (ni + n) + ni * 4 + n + 4) * 4));
-  LB_CHK(hipMalloc(&box, ni * 6 * 4));
-  LB_CHK(hipMalloc(&cost, ni * 4));
+  LB_CHK(ints.reserve(ni * 2 + (ni + n) + ni * 4 + n + 4));
+  LB_CHK(box.reserve(ni * 6));
+  LB_CHK(cost.reserve(ni));
   const int B = 256;
   const int gn = (n + B - 1) / B, gi = (int)((ni + B - 1) / B);
-  P.keys = keys_a;
-  P.ids = ids_a;
+  P.keys = keys_a.p;
+  P.ids = ids_a.p;
   hipLaunchKernelGGL(k_morton, dim3(gn), dim3(B), 0, s, P);
   LB_CHK(hipGetLastError());
-  LB_CHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys_a, keys_b, ids_a, ids_b, n, 0, 30, s));
-  LB_CHK(hipMalloc(&tmp, tmp_bytes));
-  LB_CHK(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys_a, keys_b, ids_a, ids_b, n, 0, 30, s));
-  P.keys = keys_b;
-  P.ids = ids_b;
-  P.child = ints;
+  LB_CHK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys_a.p, keys_b.p, ids_a.p, ids_b.p, n, 0, 30, s));
+  LB_CHK(tmp.reserve(tmp_bytes));
+  LB_CHK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tmp_bytes, keys_a.p, keys_b.p, ids_a.p, ids_b.p, n, 0, 30, s));
+  P.keys = keys_b.p;
+  P.ids = ids_b.p;
+  P.child = ints.p;
   P.parent = P.child + 2 * ni;
   P.start = P.parent + ni + n;
   P.range = P.start + ni;
@@ -688,21 +693,20 @@ extern "C" hipError_t ptk_build_lbvh(const LbvhIn* in, LbvhOut* out, hipStream_t
   P.flag = P.collapsed + ni;
   P.pos = P.flag + ni;
   int* counters = P.pos + n;  // n_nodes, n_out, max_stack, spare
-  P.box = box;
-  P.cost = cost;
+  P.box = box.p;
+  P.cost = cost.p;
   LB_CHK(hipMemsetAsync(counters, 0, 16, s));
-  // outputs
-  LB_CHK(hipMalloc(&out->prims, (size_t)n * sizeof(DPrim)));
-  LB_CHK(hipMalloc(&out->norms, (size_t)n * 9 * 4));
-  LB_CHK(hipMalloc(&out->prim_map, (size_t)n * 4));
-  LB_CHK(hipMalloc(&out->nodes4, (size_t)(ni + 1) * sizeof(DNode)));
-  LB_CHK(hipMalloc(&out->nodes2, ni * sizeof(DNode2)));
+  LB_CHK(o_prims.reserve((size_t)n));
+  LB_CHK(o_norms.reserve((size_t)n * 9));
+  LB_CHK(o_map.reserve((size_t)n));
+  LB_CHK(o_nodes4.reserve(ni + 1));
+  LB_CHK(o_nodes2.reserve(ni));
   // A single leaf (one BVH4 node, one child, as the host path): one primitive,
   // or as many as both the reference's LEAF_NUMBER and the leaf limit allow.
   if (n == 1 || n <= std::min(kLeafNumber, P.max_leaf)) {
     hipLaunchKernelGGL(k_identity, dim3(gn), dim3(B), 0, s, P);  // final order = sorted order
     LB_CHK(hipGetLastError());
-    hipLaunchKernelGGL(k_gather, dim3(gn), dim3(B), 0, s, P, in->norms, out->prims, out->norms, out->prim_map);
+    hipLaunchKernelGGL(k_gather, dim3(gn), dim3(B), 0, s, P, in->norms, o_prims.p, o_norms.p, o_map.p);
     LB_CHK(hipGetLastError());
     // The leaf's box from the float primitives the kernel tests, widened as
     // prim_box widens them.  (scene_min + scene_extent, rounded to nearest,
@@ -732,13 +736,13 @@ extern "C" hipError_t ptk_build_lbvh(const LbvhIn* in, LbvhOut* out, hipStream_t
     d.loz = make_float4(lo[2], inf, inf, inf);
     d.hiz = make_float4(hi[2], inf, inf, inf);
     d.ref = make_int4(~((0 << 3) | (n - 1)), ~0, ~0, ~0);
-    LB_CHK(hipMemcpyAsync(out->nodes4, &d, sizeof(d), hipMemcpyHostToDevice, s));
+    LB_CHK(hipMemcpyAsync(o_nodes4.p, &d, sizeof(d), hipMemcpyHostToDevice, s));
     DNode2 b{};
     b.a = make_float4(lo[0], hi[0], lo[1], hi[1]);
     b.b = make_float4(inf, inf, inf, inf);
     b.c = make_float4(lo[2], hi[2], inf, inf);
     b.e = make_int4(~((0 << 3) | (n - 1)), ~0, 0, 0);
-    LB_CHK(hipMemcpyAsync(out->nodes2, &b, sizeof(b), hipMemcpyHostToDevice, s));
+    LB_CHK(hipMemcpyAsync(o_nodes2.p, &b, sizeof(b), hipMemcpyHostToDevice, s));
     LB_CHK(hipStreamSynchronize(s));
     out->n4 = 1;
     out->n2 = 1;
@@ -766,43 +770,40 @@ extern "C" hipError_t ptk_build_lbvh(const LbvhIn* in, LbvhOut* out, hipStream_t
     // optimum; over the host SAH tree it pays (+10%, pt_api.cpp).
     const char* ce = std::getenv("PT_COLLAPSE");
     if (ce && std::strcmp(ce, "dp") == 0) {
-      LB_CHK(hipMalloc(&dpc, ni * 4 * sizeof(float)));
-      LB_CHK(hipMalloc(&dpk, ni * 4));
-      P.dpc = dpc;
-      P.dpk = dpk;
+      LB_CHK(dpc.reserve(ni * 4));
+      LB_CHK(dpk.reserve(ni * 4));
+      P.dpc = dpc.p;
+      P.dpk = dpk.p;
       LB_CHK(hipMemsetAsync(P.flag, 0, ni * 4, s));
       hipLaunchKernelGGL(k_dp, dim3(gn), dim3(B), 0, s, P);
       LB_CHK(hipGetLastError());
     }
     // top-down BVH4 emission (breadth first, binary node 0 -> BVH4 node 0),
     // numbering the primitives in depth-first leaf order on the way
-    Item *fa = nullptr, *fb = nullptr;
-    LB_CHK(hipMalloc(&fa, (ni + 1) * sizeof(Item)));
-    LB_CHK(hipMalloc(&fb, (ni + 1) * sizeof(Item)));
+    LB_CHK(fa.reserve(ni + 1));
+    LB_CHK(fb.reserve(ni + 1));
     Item root{0, 0, 0, 0};
     int one = 1;
-    LB_CHK(hipMemcpyAsync(fa, &root, sizeof(root), hipMemcpyHostToDevice, s));
+    LB_CHK(hipMemcpyAsync(fa.p, &root, sizeof(root), hipMemcpyHostToDevice, s));
     LB_CHK(hipMemcpyAsync(counters, &one, 4, hipMemcpyHostToDevice, s));  // n_nodes = 1 (the root)
     int n_in = 1;
     while (n_in > 0) {  // one launch per BVH4 level
       LB_CHK(hipMemsetAsync(counters + 1, 0, 4, s));
-      hipLaunchKernelGGL(k_bfs, dim3((n_in + B - 1) / B), dim3(B), 0, s, P, fa, n_in, fb, counters + 1, counters,
-                         counters + 2, out->nodes4);
+      hipLaunchKernelGGL(k_bfs, dim3((n_in + B - 1) / B), dim3(B), 0, s, P, fa.p, n_in, fb.p, counters + 1, counters,
+                         counters + 2, o_nodes4.p);
       LB_CHK(hipGetLastError());
       LB_CHK(hipMemcpyAsync(&n_in, counters + 1, 4, hipMemcpyDeviceToHost, s));
       LB_CHK(hipStreamSynchronize(s));
-      Item* t = fa;
-      fa = fb;
-      fb = t;
+      fa.swap(fb);
     }
-    hipLaunchKernelGGL(k_emit_bin, dim3(gi), dim3(B), 0, s, P, out->nodes2);
+    hipLaunchKernelGGL(k_emit_bin, dim3(gi), dim3(B), 0, s, P, o_nodes2.p);
     LB_CHK(hipGetLastError());
-    hipLaunchKernelGGL(k_gather, dim3(gn), dim3(B), 0, s, P, in->norms, out->prims, out->norms, out->prim_map);
+    hipLaunchKernelGGL(k_gather, dim3(gn), dim3(B), 0, s, P, in->norms, o_prims.p, o_norms.p, o_map.p);
     LB_CHK(hipGetLastError());
     int cnt[3] = {0, 0, 0};
     LB_CHK(hipMemcpyAsync(cnt, counters, 12, hipMemcpyDeviceToHost, s));
     float rb[6];
-    LB_CHK(hipMemcpyAsync(rb, box, 24, hipMemcpyDeviceToHost, s));
+    LB_CHK(hipMemcpyAsync(rb, box.p, 24, hipMemcpyDeviceToHost, s));
     LB_CHK(hipStreamSynchronize(s));
     out->n4 = cnt[0];
     out->n2 = (int)ni;
@@ -811,18 +812,11 @@ extern "C" hipError_t ptk_build_lbvh(const LbvhIn* in, LbvhOut* out, hipStream_t
       out->root_lo[k] = rb[k];
       out->root_hi[k] = rb[3 + k];
     }
-    (void)hipFree(fa);
-    (void)hipFree(fb);
   }
-  (void)hipFree(keys_a);
-  (void)hipFree(keys_b);
-  (void)hipFree(ids_a);
-  (void)hipFree(ids_b);
-  (void)hipFree(ints);
-  (void)hipFree(box);
-  if (dpc) (void)hipFree(dpc);
-  if (dpk) (void)hipFree(dpk);
-  (void)hipFree(cost);
-  (void)hipFree(tmp);
+  out->prims = o_prims.give();
+  out->norms = o_norms.give();
+  out->prim_map = o_map.give();
+  out->nodes4 = o_nodes4.give();
+  out->nodes2 = o_nodes2.give();
   return hipSuccess;
 }

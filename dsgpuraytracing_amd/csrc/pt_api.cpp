@@ -13,6 +13,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <cmath>
 #include <cstddef>
@@ -27,6 +28,7 @@
 #include "../../include/ptgpu_scene.h"
 #include "denoise.h"
 #include "film.h"
+#include "hip_owned.h"
 #include "launch_plan.h"
 #include "pt_device.h"
 #include "pt_error.h"
@@ -37,50 +39,37 @@ namespace {
 
 int fail(int code, const std::string& msg) { return pt_fail(code, msg); }
 
-#define HIPCHK(expr)                                                                            \
-  do {                                                                                          \
-    hipError_t _e = (expr);                                                                     \
-    if (_e != hipSuccess) return fail(PT_E_HIP, std::string(#expr ": ") + hipGetErrorString(_e)); \
+// A failed HIP call returns PT_E_HIP with the call's text; HIPCHK_ALLOC (the
+// film, denoise and reproject entry points' reserves) returns PT_E_ALLOC when
+// memory ran out, with HIP's sticky error cleared.
+#define HIPCHK_AS(expr, text, alloc)                                                              \
+  do {                                                                                            \
+    hipError_t _e = (expr);                                                                       \
+    if (_e != hipSuccess) {                                                                       \
+      if (alloc) (void)hipGetLastError();                                                         \
+      return fail((alloc) && _e == hipErrorOutOfMemory ? PT_E_ALLOC : PT_E_HIP, std::string(text ": ") + hipGetErrorString(_e)); \
+    }                                                                                             \
   } while (0)
-
-template <class T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  hipError_t reserve(size_t count) {
-    if (count <= n && p) return hipSuccess;
-    if (p) {  // renders in flight on other streams may still read the old array
-      (void)hipDeviceSynchronize();
-      (void)hipFree(p);
-    }
-    p = nullptr;
-    n = 0;
-    hipError_t e = hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) n = std::max<size_t>(count, 1);
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  void adopt(T* q, size_t count) {  // take ownership of a hipMalloc'd array
-    release();
-    p = q;
-    n = count;
-  }
-};
+#define HIPCHK(expr) HIPCHK_AS(expr, #expr, false)
+#define HIPCHK_ALLOC(expr) HIPCHK_AS(expr, #expr, true)
 
 // A device list with a host mirror of what it holds: uploaded (on `s`) only
 // when it changed -- the lists rarely change between frames.  Never a null
 // device list: an empty one (a launch may cull every block) still has an array.
+// `alloc`: a film entry point's list (PT_E_ALLOC when memory runs out).
 template <class D, class T>
-int sync_list(DevBuf<D>& dev, std::vector<T>& mirror, const T* list, size_t n, hipStream_t s) {
+int sync_list(DevBuf<D>& dev, std::vector<T>& mirror, const T* list, size_t n, hipStream_t s, bool alloc = false) {
   static_assert(sizeof(D) == sizeof(T), "the list uploads without conversion");
-  HIPCHK(dev.reserve(n));
+  const D* held = dev.p;
+  const hipError_t r = dev.reserve(n);
+  if (dev.p != held) mirror.clear();  // (a new array holds nothing yet)
+  HIPCHK_AS(r, "dev.reserve(n)", alloc);
   if (n == mirror.size() && std::memcmp(list, mirror.data(), n * sizeof(T)) == 0) return PT_OK;
-  mirror.assign(list, list + n);
-  if (n) HIPCHK(hipMemcpyAsync(dev.p, mirror.data(), n * sizeof(T), hipMemcpyHostToDevice, s));
+  mirror.assign(list, list + n);  // (the copy's source outlives the call)
+  if (n == 0) return PT_OK;
+  const hipError_t e = hipMemcpyAsync(dev.p, mirror.data(), n * sizeof(T), hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) mirror.clear();  // (not what the device holds)
+  HIPCHK(e);
   return PT_OK;
 }
 
@@ -100,21 +89,28 @@ int put(DevBuf<T>& dev, const std::vector<T>& v) {
 // the caller's stream at high priority: every arm that keeps more than four
 // hardware queues busy -- counting torch's collective stream on a rank of an
 // N-GPU run -- was slower (N = 8 share 0.22 -> 0.29-0.38 ms per frame).
-static hipError_t make_render_stream(hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }
+hipError_t make_render_stream(Stream& s) { return s.create(hipStreamNonBlocking); }
+
+// The frame sizes the kernels' 16-bit pixel coordinates and 32-bit pixel indices hold.
+int check_frame_dims(int64_t width, int64_t height, const char* fn) {
+  if (width < 1 || height < 1 || width > 65535 || height > 65535 || width * height > (int64_t)1 << 30)
+    return fail(PT_E_INVALID, std::string(fn) + ": width and height must be 1 .. 65535 and width * height <= 2^30");
+  return PT_OK;
+}
 
 }  // namespace
 
 struct pt_ctx {
   int device = 0;
-  hipStream_t stream = nullptr;
+  Stream stream;
   // launch timing: a ring of (render start, render end, resolve end) event
   // triples so device renders need not synchronise (pt_get_launch_times)
   static constexpr int kRing = 256;
-  hipEvent_t ev[kRing][3] = {};
+  Event ev[kRing][3];
   int64_t n_launches = 0;   // launches recorded so far (ring slot = index % kRing)
   bool census_valid = false;  // the last launch was a PT_CENSUS plain launch (its trace area holds start/end/CU)
   bool times_pending = false;  // c->last's times belong to a launch not yet synchronised
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;  // the current launch's triple
+  const Event* cur = nullptr;  // the current launch's triple (of `ev`)
   DevBuf<DNode> nodes;    // the render tree (BVH4)
   DevBuf<DNode2> nodes2;  // binary tree for PT_FLAG_REF_COUNTS
   DevBuf<int> prim_map;   // own BVH order (SAH or GPU-built) -> uploaded primitive index (else empty)
@@ -146,8 +142,8 @@ struct pt_ctx {
   static constexpr int kSlotsLarge = 2;
   uint64_t slot_rr = 0;      // launches issued on the pipeline (slot rotation)
   bool small_last = false;   // the previous launch was small: rotate over every slot
-  hipStream_t rstream[kSlots] = {};
-  hipEvent_t ev_free[kSlots] = {};
+  Stream rstream[kSlots];
+  Event ev_free[kSlots];
   DevBuf<int4> tiles[kSlots];
   std::vector<PlanRect> tiles_host[kSlots];  // what `tiles` holds
   DevBuf<int4> blocks[kSlots];           // footprint-clipped 8x8 pixel blocks of the tiles
@@ -179,18 +175,17 @@ struct pt_ctx {
   };
   struct TileBatch {
     std::vector<TileJob> jobs;
-    float* stage = nullptr;  // pinned: rows y0 .. y0 + rows - 1 of the frame
-    size_t cap = 0;          // floats the stage holds
+    PinnedBuf<float> stage;  // rows y0 .. y0 + rows - 1 of the frame
     int y0 = 0, W = 0, H = 0;
-    hipEvent_t ev = nullptr;
+    Event ev;
   };
   std::vector<TileJob> tq;
   int tile_batch = 256;  // tiles per launch (PT_TILE_BATCH): 256 beat 16-128 and 1024 (profiles/r3/seam_native_batch_sweep.txt)
   int fault_tile_launch = 0, n_tile_launches = 0;  // PT_FAULT_TILE_LAUNCH (tests)
   std::mutex tmu;
   std::condition_variable tcv;
-  std::deque<TileBatch*> tpending;  // rendered batches awaiting completion, in launch order
-  std::vector<TileBatch*> tfree;    // completed batches: stages and events for reuse
+  std::deque<std::unique_ptr<TileBatch>> tpending;  // rendered batches awaiting completion, in launch order
+  std::vector<std::unique_ptr<TileBatch>> tfree;    // completed batches: stages and events for reuse
   int tinflight = 0;                // batches launched and not yet completed
   int terr = PT_OK;                 // first completion error (reported by pt_tile_finish)
   std::string terrmsg;
@@ -215,29 +210,30 @@ struct pt_ctx {
   int grid_plain = 0, grid_stats = 0;
   int bpc_plain = 0, bpc_stats = 0, n_cu = 0;
   int bpc_variant[4] = {0, 0, 0, 0};  // plain builds: [env * 2 + gtab] (the common one is bpc_plain)
-  std::vector<pt_film*> films;  // films not yet destroyed (pt_destroy frees them)
+  std::vector<std::unique_ptr<pt_film>> films;  // films not yet destroyed
   DevBuf<uint32_t> tc_thr;      // pt_to_color_thresholds on the device (uploaded at first use)
   bool tc_thr_ready = false;
   // first-hit feature pass (pt_render_features*): its tile list, stack spill
   // area and the device side of the host entry point's output; a pass that
-  // comes on another stream than the last waits for the last one's event
+  // comes on another stream than the last waits for it
   DevBuf<int4> ftiles;
   std::vector<int4> ftiles_host;
   DevBuf<int> f_spill;
   DevBuf<float4> feat_out;
-  hipEvent_t ev_feat = nullptr;
-  hipStream_t feat_stream = nullptr;
-  bool feat_ordered = false;
+  StreamOrder feat_order;
   DevBuf<float4> dn_a, dn_b;  // pt_denoise_device: the iterations' ping-pong records (grown on demand)
   // reprojection (pt_reproject_device, pt_film_reproject): the uploaded scene's
   // BSDF types, and the keep table on the device with what it holds; a gather
-  // that comes on another stream than the last waits for the last one's event
+  // that comes on another stream than the last waits for it
   std::vector<int32_t> bsdf_types;
   DevBuf<uint32_t> rp_keep;
   std::vector<uint32_t> rp_keep_host;
-  hipEvent_t ev_rp = nullptr;
-  hipStream_t rp_stream = nullptr;
-  bool rp_ordered = false;
+  StreamOrder rp_order;
+  // Every member frees itself, in reverse order of declaration; only what
+  // needs ordering is done here: no kernel and no completion may still be
+  // running when the first member goes.  (The completion thread and its
+  // batches are declared after `frame`, which they read.)
+  ~pt_ctx();
 };
 
 // A progressive film (ptgpu.h: pt_film_*; kernels and record layout: film.h).
@@ -262,20 +258,20 @@ struct pt_film {
   DevBuf<uint4> rec2;
   DevBuf<float4> feat2;
   DevBuf<unsigned long long> rp_counts;
-  hipEvent_t ev_rp[2] = {};
+  Event ev_rp[2];
   bool rp_timed = false;
   uint64_t next = 0;     // next sample index (<= 2^32)
   int64_t passes = 0;
-  hipEvent_t ev_acc[2] = {}, ev_res[2] = {};  // around the last accumulate / resolve kernel
+  Event ev_acc[2], ev_res[2];  // around the last accumulate / resolve kernel
   bool acc_timed = false, res_timed = false;
   // the film's last operation: a later one on another stream waits for it
-  hipEvent_t ev_order = nullptr;
-  hipStream_t last_stream = nullptr;
-  bool ordered = false;  // ev_order has been recorded
+  StreamOrder order;
 };
 
-extern "C" {
+// The stream an entry point runs on: the caller's, or the context's for NULL.
+static hipStream_t stream_of(const pt_ctx* c, void* stream) { return stream ? (hipStream_t)stream : (hipStream_t)c->stream; }
 
+extern "C" {
 
 int pt_create(int device, pt_ctx** out) {
   if (!out) return fail(PT_E_INVALID, "pt_create: out is NULL");
@@ -284,23 +280,23 @@ int pt_create(int device, pt_ctx** out) {
   HIPCHK(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) return fail(PT_E_INVALID, "pt_create: no such HIP device");
   HIPCHK(hipSetDevice(device));
-  pt_ctx* c = new pt_ctx();
+  std::unique_ptr<pt_ctx> c(new pt_ctx());  // (a failure below frees what was acquired so far)
   c->device = device;
-  HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  HIPCHK(c->stream.create(hipStreamNonBlocking));
   for (int k = 0; k < pt_ctx::kSlots; ++k) {
     // (slots past the first two get their stream when a small launch first
     // uses them: HIP maps streams onto GPU_MAX_HW_QUEUES hardware queues, 4 by
     // default, and two more streams per context put the render streams of
     // large frames on shared queues -- C3 pipelined -12%)
     if (k < pt_ctx::kSlotsLarge) {
-      HIPCHK(make_render_stream(&c->rstream[k]));
-      HIPCHK(hipEventCreateWithFlags(&c->ev_free[k], hipEventDisableTiming));
+      HIPCHK(make_render_stream(c->rstream[k]));
+      HIPCHK(c->ev_free[k].create(hipEventDisableTiming));
       HIPCHK(hipEventRecord(c->ev_free[k], c->stream));
     }
     HIPCHK(c->counter[k].reserve(PT_QUEUE_WORDS * PT_QUEUE_HEADS));  // work-queue heads, one 128-B line each
   }
   for (auto& tri : c->ev)
-    for (auto& e : tri) HIPCHK(hipEventCreate(&e));
+    for (auto& e : tri) HIPCHK(e.create());
   HIPCHK(c->stats.reserve(PT_STATS_SLOTS));
   hipDeviceProp_t prop;
   HIPCHK(hipGetDeviceProperties(&prop, device));
@@ -320,62 +316,25 @@ int pt_create(int device, pt_ctx** out) {
   if (const char* f = std::getenv("PT_FAULT_TILE_LAUNCH")) c->fault_tile_launch = std::atoi(f);
   // counters + one trace record per wave of the largest stats grid
   HIPCHK(c->stats.reserve(PT_STATS_SLOTS + (size_t)PT_WAVE_TRACE * std::max(c->grid_stats, 64 * c->n_cu)));
-  *out = c;
+  *out = c.release();
   return PT_OK;
 }
 
-static void tile_worker_stop(pt_ctx* c);
-static void film_free(pt_film* f);
+pt_ctx::~pt_ctx() {
+  (void)hipSetDevice(device);
+  (void)hipDeviceSynchronize();  // no render of this context may still be running
+  if (tworker.joinable()) {
+    {
+      std::lock_guard<std::mutex> lk(tmu);
+      tstop = true;
+    }
+    tcv.notify_all();
+    tworker.join();  // drains the pending batches first
+  }
+}
 
 int pt_destroy(pt_ctx* c) {
   if (!c) return PT_OK;
-  (void)hipSetDevice(c->device);
-  (void)hipDeviceSynchronize();  // no render of this context may still be running
-  for (pt_film* f : c->films) film_free(f);
-  c->films.clear();
-  c->tc_thr.release();
-  c->ftiles.release();
-  c->f_spill.release();
-  c->feat_out.release();
-  c->dn_a.release();
-  c->dn_b.release();
-  c->rp_keep.release();
-  if (c->ev_feat) (void)hipEventDestroy(c->ev_feat);
-  if (c->ev_rp) (void)hipEventDestroy(c->ev_rp);
-  c->nodes.release();
-  c->nodes2.release();
-  c->prim_map.release();
-  c->env_tex.release();
-  c->env_ptheta.release();
-  c->env_pphi.release();
-  c->env_pdf.release();
-  c->env_rtheta.release();
-  c->env_rphi.release();
-  c->prims.release();
-  c->norms.release();
-  c->bsdfs.release();
-  c->lights.release();
-  for (int k = 0; k < pt_ctx::kSlots; ++k) {
-    c->tiles[k].release();
-    c->blocks[k].release();
-    c->tblock0[k].release();
-    c->tout[k].release();
-    c->spill[k].release();
-    c->partial[k].release();
-    c->counter[k].release();
-    if (c->ev_free[k]) (void)hipEventDestroy(c->ev_free[k]);
-    if (c->rstream[k]) (void)hipStreamDestroy(c->rstream[k]);
-  }
-  tile_worker_stop(c);
-  c->q_spill.release();
-  c->frame.release();
-  c->stats.release();
-  c->q_f.release();
-  c->q_i.release();
-  for (auto& tri : c->ev)
-    for (auto& e : tri)
-      if (e) (void)hipEventDestroy(e);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return PT_OK;
 }
@@ -429,8 +388,11 @@ static int upload_impl(pt_ctx* c, const pt_scene* s, bool gpu_bvh) {
 
   const FlattenKnobs knobs = read_flatten_knobs(gpu_bvh);
   FlatScene f;
-  if (int rc = flatten_scene(s, knobs, f)) return rc;
+  if (int rc = flatten_scene(s, knobs, f)) return rc;  // (a scene refused so far leaves the old one in place)
 
+  // from here on the device holds a mix of the old scene and the new: a
+  // failure half-way leaves no scene, not one whose arrays disagree
+  c->have_scene = false;
   if (int rc = put(c->prims, f.prims)) return rc;
   if (int rc = put(c->norms, f.norms)) return rc;
   HIPCHK(c->bsdfs.reserve(f.bsdfs.size()));
@@ -513,9 +475,7 @@ int pt_set_params(pt_ctx* c, const pt_params* p) {
     return fail(PT_E_INVALID, "pt_set_params: width/height/spp/ns_area_light must be positive, max_depth >= 0");
   if (p->max_depth > 254 || p->ns_area_light > 255)  // packed in 8 bits each in the kernel's path state
     return fail(PT_E_INVALID, "pt_set_params: max_depth must be <= 254 and ns_area_light <= 255");
-  if ((int64_t)p->width * p->height > (int64_t)1 << 30) return fail(PT_E_INVALID, "pt_set_params: frame too large");
-  if (p->width > 65535 || p->height > 65535)  // pixel coordinates are packed in 16 bits each in the kernel
-    return fail(PT_E_INVALID, "pt_set_params: width and height must be <= 65535");
+  if (int rc = check_frame_dims(p->width, p->height, "pt_set_params")) return rc;
   c->params = *p;
   c->have_params = true;
   return PT_OK;
@@ -689,8 +649,8 @@ static int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs,
   if (!plan.stats) c->small_last = plan.small;
   const bool idle = pipelined && gpu_idle;
   if (!c->rstream[slot]) {  // a small launch's first use of slots 2 and 3
-    HIPCHK(make_render_stream(&c->rstream[slot]));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_free[slot], hipEventDisableTiming));
+    HIPCHK(make_render_stream(c->rstream[slot]));
+    HIPCHK(c->ev_free[slot].create(hipEventDisableTiming));
     HIPCHK(hipEventRecord(c->ev_free[slot], c->stream));
   }
   hipStream_t rs = pipelined && !idle ? c->rstream[slot] : s;
@@ -735,17 +695,11 @@ static int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs,
   P.stack_spill = plan.spill_ints ? c->spill[slot].p : nullptr;
   if (P.census)  // (a build without -DPT_CENSUS=1 leaves the drain fields 0)
     HIPCHK(hipMemsetAsync(c->stats.p + PT_STATS_SLOTS, 0, (size_t)plan.grid * PT_WAVE_TRACE * 8, rs));
-  {
-    hipEvent_t* tri = c->ev[c->n_launches % pt_ctx::kRing];
-    c->ev0 = tri[0];
-    c->ev1 = tri[1];
-    c->ev2 = tri[2];
-    ++c->n_launches;
-  }
-  HIPCHK(hipEventRecord(c->ev0, rs));
+  c->cur = c->ev[c->n_launches++ % pt_ctx::kRing];
+  HIPCHK(hipEventRecord(c->cur[0], rs));
   HIPCHK(ptk_launch_render(&P, plan.grid, plan.stats, (flags & PT_FLAG_REF_COUNTS) != 0, rs));
-  HIPCHK(hipEventRecord(c->ev1, rs));
-  if (rs != s) HIPCHK(hipStreamWaitEvent(s, c->ev1, 0));  // the resolve reads the finished group sums
+  HIPCHK(hipEventRecord(c->cur[1], rs));
+  if (rs != s) HIPCHK(hipStreamWaitEvent(s, c->cur[1], 0));  // the resolve reads the finished group sums
   for (int f = 0; f < nf; ++f) {  // (a frame batch: frame f's sums follow frame f - 1's)
     KParams Pf = P;
     Pf.partial = P.partial + 3 * (size_t)f * (size_t)plan.frame_slots;
@@ -753,7 +707,7 @@ static int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs,
     HIPCHK(ptk_launch_resolve(&Pf, s));
   }
   c->counter_clean[slot] = true;  // (the resolve zeroed the slot's queue heads)
-  HIPCHK(hipEventRecord(c->ev2, s));
+  HIPCHK(hipEventRecord(c->cur[2], s));
   HIPCHK(hipEventRecord(c->ev_free[slot], s));
   c->census_valid = P.census != 0;
   c->culled_px = plan.culled_px;
@@ -774,11 +728,11 @@ static int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs,
 // The last launch's kernel / resolve times (waits for its events).
 static int settle_times(pt_ctx* c) {
   if (!c->times_pending) return PT_OK;
-  HIPCHK(hipEventSynchronize(c->ev2));
+  HIPCHK(hipEventSynchronize(c->cur[2]));
   float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
+  HIPCHK(hipEventElapsedTime(&ms, c->cur[0], c->cur[1]));
   c->last.last_ms = ms;
-  HIPCHK(hipEventElapsedTime(&ms, c->ev1, c->ev2));
+  HIPCHK(hipEventElapsedTime(&ms, c->cur[1], c->cur[2]));
   c->last.resolve_ms = ms;
   c->times_pending = false;
   return PT_OK;
@@ -907,63 +861,21 @@ int pt_render_tiles_device(pt_ctx* c, const pt_tile* tiles, int32_t n_tiles, flo
   std::vector<int4> tl;
   if ((rc = build_tiles(c, tiles, n_tiles, tl))) return rc;
   if (int rc2 = check_packed(c, tiles, n_tiles, flags, "pt_render_tiles_device")) return rc2;
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s = stream_of(c, stream);
   if ((rc = launch(c, tl, &hdr_out_dev, 1, nullptr, s, flags))) return rc;
   return finish_stats(c, s, flags, false);
 }
 
 // ---- progressive film (ptgpu.h: pt_film_*; kernels and record layout: film.hip, film.h)
-#define FILM_ALLOC(expr)                                                                        \
-  do {                                                                                          \
-    hipError_t _e = (expr);                                                                     \
-    if (_e != hipSuccess) {                                                                     \
-      (void)hipGetLastError();                                                                  \
-      return fail(_e == hipErrorOutOfMemory ? PT_E_ALLOC : PT_E_HIP, std::string(#expr ": ") + hipGetErrorString(_e)); \
-    }                                                                                           \
-  } while (0)
-
-static void film_free(pt_film* f) {
-  f->rec.release();
-  f->pass.release();
-  f->tiles.release();
-  f->etiles.release();
-  f->emax.release();
-  f->out_hdr.release();
-  f->out_err.release();
-  f->out_rgba.release();
-  f->feat.release();
-  f->cv[0].release();
-  f->cv[1].release();
-  f->rec2.release();
-  f->feat2.release();
-  f->rp_counts.release();
-  for (hipEvent_t e : {f->ev_acc[0], f->ev_acc[1], f->ev_res[0], f->ev_res[1], f->ev_order, f->ev_rp[0], f->ev_rp[1]})
-    if (e) (void)hipEventDestroy(e);
-  delete f;
-}
-
 // The toColor thresholds on the device (once per context; a blocking copy, so
 // every kernel queued afterwards sees them).
 static int tonemap_table(pt_ctx* c) {
   if (c->tc_thr_ready) return PT_OK;
   uint32_t thr[256];
   if (int rc = pt_to_color_thresholds(thr)) return rc;
-  FILM_ALLOC(c->tc_thr.reserve(256));
+  HIPCHK_ALLOC(c->tc_thr.reserve(256));
   HIPCHK(hipMemcpy(c->tc_thr.p, thr, sizeof(thr), hipMemcpyHostToDevice));
   c->tc_thr_ready = true;
-  return PT_OK;
-}
-
-// Consecutive operations on one film are ordered: one that comes on another
-// stream than the last waits for the last one's event.
-static int film_begin(pt_film* f, hipStream_t s) {
-  if (f->ordered && f->last_stream != s) HIPCHK(hipStreamWaitEvent(s, f->ev_order, 0));
-  return PT_OK;
-}
-static int film_end(pt_film* f, hipStream_t s) {
-  HIPCHK(hipEventRecord(f->ev_order, s));
-  f->last_stream = s;
-  f->ordered = true;
   return PT_OK;
 }
 
@@ -982,29 +894,21 @@ static bool rects_disjoint(std::vector<int4>& r) {
 int pt_film_create(pt_ctx* c, int32_t width, int32_t height, pt_film** out) {
   if (out) *out = nullptr;
   if (!c || !out) return fail(PT_E_INVALID, "pt_film_create: NULL argument");
-  if (width < 1 || height < 1 || width > 65535 || height > 65535 || (int64_t)width * height > (int64_t)1 << 30)
-    return fail(PT_E_INVALID, "pt_film_create: width and height must be 1 .. 65535 and width * height <= 2^30");
+  if (int rc = check_frame_dims(width, height, "pt_film_create")) return rc;
   HIPCHK(hipSetDevice(c->device));
   if (int rc = tonemap_table(c)) return rc;
-  pt_film* f = new pt_film();
+  std::unique_ptr<pt_film> f(new pt_film());
   f->ctx = c;
   f->W = width;
   f->H = height;
   const size_t px = (size_t)width * (size_t)height;
-  int rc = [&]() -> int {
-    FILM_ALLOC(f->rec.reserve(2 * px));
-    FILM_ALLOC(f->pass.reserve(3 * px));
-    for (hipEvent_t* e : {&f->ev_acc[0], &f->ev_acc[1], &f->ev_res[0], &f->ev_res[1]}) HIPCHK(hipEventCreate(e));
-    HIPCHK(hipEventCreateWithFlags(&f->ev_order, hipEventDisableTiming));
-    HIPCHK(hipMemsetAsync(f->rec.p, 0, 2 * px * sizeof(uint4), c->stream));
-    return film_end(f, c->stream);
-  }();
-  if (rc) {
-    film_free(f);
-    return rc;
-  }
-  c->films.push_back(f);
-  *out = f;
+  HIPCHK_ALLOC(f->rec.reserve(2 * px));
+  HIPCHK_ALLOC(f->pass.reserve(3 * px));
+  for (Event* e : {&f->ev_acc[0], &f->ev_acc[1], &f->ev_res[0], &f->ev_res[1]}) HIPCHK(e->create());
+  HIPCHK(hipMemsetAsync(f->rec.p, 0, 2 * px * sizeof(uint4), c->stream));
+  HIPCHK(f->order.end(c->stream));
+  *out = f.get();
+  c->films.push_back(std::move(f));
   return PT_OK;
 }
 
@@ -1013,8 +917,8 @@ int pt_film_destroy(pt_film* f) {
   pt_ctx* c = f->ctx;
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();  // no kernel may still use the film's memory
-  c->films.erase(std::remove(c->films.begin(), c->films.end(), f), c->films.end());
-  film_free(f);
+  c->films.erase(std::remove_if(c->films.begin(), c->films.end(), [f](const auto& o) { return o.get() == f; }),
+                 c->films.end());
   return PT_OK;
 }
 
@@ -1022,13 +926,14 @@ int pt_film_clear(pt_film* f, void* stream) {
   if (!f) return fail(PT_E_INVALID, "pt_film_clear: NULL film");
   pt_ctx* c = f->ctx;
   HIPCHK(hipSetDevice(c->device));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  if (int rc = film_begin(f, s)) return rc;
+  hipStream_t s = stream_of(c, stream);
+  HIPCHK(f->order.begin(s));
   HIPCHK(hipMemsetAsync(f->rec.p, 0, 2 * (size_t)f->W * (size_t)f->H * sizeof(uint4), s));
   f->next = 0;
   f->passes = 0;
   f->have_feat = false;
-  return film_end(f, s);
+  HIPCHK(f->order.end(s));
+  return PT_OK;
 }
 
 int pt_film_set_next_sample(pt_film* f, uint32_t next_sample) {
@@ -1068,8 +973,8 @@ int pt_film_add_pass(pt_film* f, const pt_tile* tiles, int32_t n_tiles, void* st
   for (const int4& r : rects)
     for (int y = r.y; y < r.w; y += 32)
       for (int x = r.x; x < r.z; x += 32) tl.push_back(make_int4(x, y, std::min(32, r.z - x), std::min(32, r.w - y)));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  if ((rc = film_begin(f, s))) return rc;
+  hipStream_t s = stream_of(c, stream);
+  HIPCHK(f->order.begin(s));
   // the pass: the context's params with the film's sample index, through the
   // render path every other entry point uses; the stored params stay the caller's
   const uint32_t base = c->params.sample_base;
@@ -1080,14 +985,7 @@ int pt_film_add_pass(pt_film* f, const pt_tile* tiles, int32_t n_tiles, void* st
   if (rc) return rc;
   if ((rc = finish_stats(c, s, 0, false))) return rc;
   if (!tl.empty()) {
-    if (tl.size() != f->tiles_host.size() || std::memcmp(tl.data(), f->tiles_host.data(), tl.size() * sizeof(int4)) != 0) {
-      f->tiles_host.clear();  // (not what the device holds, should the upload fail)
-      FILM_ALLOC(f->tiles.reserve(tl.size()));
-      f->tiles_host = tl;  // (the copy's source outlives the call)
-      const hipError_t e = hipMemcpyAsync(f->tiles.p, f->tiles_host.data(), tl.size() * sizeof(int4), hipMemcpyHostToDevice, s);
-      if (e != hipSuccess) f->tiles_host.clear();
-      HIPCHK(e);
-    }
+    if ((rc = sync_list(f->tiles, f->tiles_host, tl.data(), tl.size(), s, true))) return rc;
     FilmAccArgs a;
     a.tiles = f->tiles.p;
     a.rec = f->rec.p;
@@ -1102,7 +1000,8 @@ int pt_film_add_pass(pt_film* f, const pt_tile* tiles, int32_t n_tiles, void* st
   }
   f->next += (uint64_t)P.spp;
   ++f->passes;
-  return film_end(f, s);
+  HIPCHK(f->order.end(s));
+  return PT_OK;
 }
 
 int pt_film_resolve_device(pt_film* f, float* hdr_dev, uint32_t* rgba_dev, float* err_dev, void* stream) {
@@ -1110,8 +1009,8 @@ int pt_film_resolve_device(pt_film* f, float* hdr_dev, uint32_t* rgba_dev, float
   if (!hdr_dev && !rgba_dev && !err_dev) return PT_OK;
   pt_ctx* c = f->ctx;
   HIPCHK(hipSetDevice(c->device));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  if (int rc = film_begin(f, s)) return rc;
+  hipStream_t s = stream_of(c, stream);
+  HIPCHK(f->order.begin(s));
   FilmResolveArgs a;
   a.rec = f->rec.p;
   a.thr = c->tc_thr.p;
@@ -1124,7 +1023,8 @@ int pt_film_resolve_device(pt_film* f, float* hdr_dev, uint32_t* rgba_dev, float
   HIPCHK(ptk_film_resolve(&a, s));
   HIPCHK(hipEventRecord(f->ev_res[1], s));
   f->res_timed = true;
-  return film_end(f, s);
+  HIPCHK(f->order.end(s));
+  return PT_OK;
 }
 
 int pt_film_resolve(pt_film* f, float* hdr_host, uint32_t* rgba_host, float* err_host) {
@@ -1132,9 +1032,9 @@ int pt_film_resolve(pt_film* f, float* hdr_host, uint32_t* rgba_host, float* err
   pt_ctx* c = f->ctx;
   HIPCHK(hipSetDevice(c->device));
   const size_t px = (size_t)f->W * (size_t)f->H;
-  if (hdr_host) FILM_ALLOC(f->out_hdr.reserve(3 * px));
-  if (rgba_host) FILM_ALLOC(f->out_rgba.reserve(px));
-  if (err_host) FILM_ALLOC(f->out_err.reserve(px));
+  if (hdr_host) HIPCHK_ALLOC(f->out_hdr.reserve(3 * px));
+  if (rgba_host) HIPCHK_ALLOC(f->out_rgba.reserve(px));
+  if (err_host) HIPCHK_ALLOC(f->out_err.reserve(px));
   if (int rc = pt_film_resolve_device(f, hdr_host ? f->out_hdr.p : nullptr, rgba_host ? f->out_rgba.p : nullptr,
                                       err_host ? f->out_err.p : nullptr, nullptr))
     return rc;
@@ -1160,10 +1060,10 @@ int pt_film_tile_error(pt_film* f, const pt_tile* tiles, int32_t n_tiles, float*
   }
   pt_ctx* c = f->ctx;
   HIPCHK(hipSetDevice(c->device));
-  FILM_ALLOC(f->etiles.reserve(tl.size()));
-  FILM_ALLOC(f->emax.reserve(tl.size()));
+  HIPCHK_ALLOC(f->etiles.reserve(tl.size()));
+  HIPCHK_ALLOC(f->emax.reserve(tl.size()));
   hipStream_t s = c->stream;
-  if (int rc = film_begin(f, s)) return rc;
+  HIPCHK(f->order.begin(s));
   HIPCHK(hipMemcpyAsync(f->etiles.p, tl.data(), tl.size() * sizeof(int4), hipMemcpyHostToDevice, s));
   FilmErrArgs a;
   a.tiles = f->etiles.p;
@@ -1173,7 +1073,7 @@ int pt_film_tile_error(pt_film* f, const pt_tile* tiles, int32_t n_tiles, float*
   a.H = f->H;
   HIPCHK(ptk_film_tile_error(&a, n_tiles, s));
   HIPCHK(hipMemcpyAsync(err_host, f->emax.p, tl.size() * sizeof(float), hipMemcpyDeviceToHost, s));
-  if (int rc = film_end(f, s)) return rc;
+  HIPCHK(f->order.end(s));
   HIPCHK(hipStreamSynchronize(s));
   return PT_OK;
 }
@@ -1214,17 +1114,16 @@ int pt_to_color_device(pt_ctx* c, const float* hdr_dev, int32_t width, int32_t h
   a.thr = c->tc_thr.p;
   a.rgba = rgba_dev;
   a.W = width;
-  HIPCHK(ptk_to_color(&a, stream ? (hipStream_t)stream : c->stream));
+  HIPCHK(ptk_to_color(&a, stream_of(c, stream)));
   return PT_OK;
 }
 
 // ---- first-hit feature buffers (ptgpu.h: pt_render_features*; kernel: pt_kernels.hip features_kernel)
 static int features_launch(pt_ctx* c, const std::vector<int4>& tl, float4* feat, hipStream_t s) {
   if (tl.empty()) return PT_OK;
-  if (!c->ev_feat) HIPCHK(hipEventCreateWithFlags(&c->ev_feat, hipEventDisableTiming));
   // the tile list and the spill area are the context's: a pass on another
   // stream than the last one's waits for it
-  if (c->feat_ordered && c->feat_stream != s) HIPCHK(hipStreamWaitEvent(s, c->ev_feat, 0));
+  HIPCHK(c->feat_order.begin(s));
   if (int rc = sync_list(c->ftiles, c->ftiles_host, tl.data(), tl.size(), s)) return rc;
   FeatArgs A;
   std::memset(&A, 0, sizeof(A));
@@ -1250,9 +1149,7 @@ static int features_launch(pt_ctx* c, const std::vector<int4>& tl, float4* feat,
     A.stack_spill = c->f_spill.p;
   }
   HIPCHK(ptk_launch_features(&A, (int)tl.size(), s));
-  HIPCHK(hipEventRecord(c->ev_feat, s));
-  c->feat_stream = s;
-  c->feat_ordered = true;
+  HIPCHK(c->feat_order.end(s));
   return PT_OK;
 }
 
@@ -1265,7 +1162,7 @@ int pt_render_features_device(pt_ctx* c, const pt_tile* tiles, int32_t n_tiles, 
   HIPCHK(hipSetDevice(c->device));
   std::vector<int4> tl;
   if ((rc = build_tiles(c, tiles, n_tiles, tl))) return rc;
-  return features_launch(c, tl, (float4*)feat_dev, stream ? (hipStream_t)stream : c->stream);
+  return features_launch(c, tl, (float4*)feat_dev, stream_of(c, stream));
 }
 
 int pt_render_features(pt_ctx* c, const pt_tile* tiles, int32_t n_tiles, void* feat_host) {
@@ -1339,16 +1236,15 @@ int pt_denoise_device(pt_ctx* c, const float* cv_dev, const void* feat_dev, int3
   pt_denoise_params prm;
   if (int rc = denoise_params(params, &prm, "pt_denoise_device")) return rc;
   if (!c || !cv_dev || !feat_dev || !out_cv_dev) return fail(PT_E_INVALID, "pt_denoise_device: NULL argument");
-  if (width < 1 || height < 1 || width > 65535 || height > 65535 || (int64_t)width * height > (int64_t)1 << 30)
-    return fail(PT_E_INVALID, "pt_denoise_device: width and height must be 1 .. 65535 and width * height <= 2^30");
+  if (int rc = check_frame_dims(width, height, "pt_denoise_device")) return rc;
   const size_t px = (size_t)width * (size_t)height;
   const uintptr_t a0 = (uintptr_t)cv_dev, b0 = (uintptr_t)out_cv_dev, len = px * sizeof(float4);
   if (a0 < b0 + len && b0 < a0 + len) return fail(PT_E_INVALID, "pt_denoise_device: input and output overlap");
   HIPCHK(hipSetDevice(c->device));
-  if (prm.iterations > 1) FILM_ALLOC(c->dn_a.reserve(px));
-  if (prm.iterations > 2) FILM_ALLOC(c->dn_b.reserve(px));
+  if (prm.iterations > 1) HIPCHK_ALLOC(c->dn_a.reserve(px));
+  if (prm.iterations > 2) HIPCHK_ALLOC(c->dn_b.reserve(px));
   return denoise_chain((const float4*)cv_dev, (const float4*)feat_dev, width, height, prm, c->dn_a.p, c->dn_b.p,
-                       (float4*)out_cv_dev, stream ? (hipStream_t)stream : c->stream);
+                       (float4*)out_cv_dev, stream_of(c, stream));
 }
 
 static int film_frame_check(const pt_film* f, const char* fn) {
@@ -1371,14 +1267,15 @@ int pt_film_set_features(pt_film* f, const pt_tile* tiles, int32_t n_tiles, void
   HIPCHK(hipSetDevice(c->device));
   std::vector<int4> tl;
   if ((rc = build_tiles(c, tiles, n_tiles, tl))) return rc;
-  FILM_ALLOC(f->feat.reserve(2 * (size_t)f->W * (size_t)f->H));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  if ((rc = film_begin(f, s))) return rc;
+  HIPCHK_ALLOC(f->feat.reserve(2 * (size_t)f->W * (size_t)f->H));
+  hipStream_t s = stream_of(c, stream);
+  HIPCHK(f->order.begin(s));
   if (!f->have_feat) HIPCHK(ptk_features_clear(f->feat.p, f->W, f->H, s));  // a pixel never covered: the miss record
   if ((rc = features_launch(c, tl, f->feat.p, s))) return rc;
   f->have_feat = true;
   f->feat_cam = c->cam;
-  return film_end(f, s);
+  HIPCHK(f->order.end(s));
+  return PT_OK;
 }
 
 int pt_film_denoise_device(pt_film* f, const pt_denoise_params* params, float* hdr_dev, uint32_t* rgba_dev,
@@ -1393,10 +1290,10 @@ int pt_film_denoise_device(pt_film* f, const pt_denoise_params* params, float* h
   pt_ctx* c = f->ctx;
   HIPCHK(hipSetDevice(c->device));
   const size_t px = (size_t)f->W * (size_t)f->H;
-  FILM_ALLOC(f->cv[0].reserve(px));
-  FILM_ALLOC(f->cv[1].reserve(px));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  if (int rc = film_begin(f, s)) return rc;
+  HIPCHK_ALLOC(f->cv[0].reserve(px));
+  HIPCHK_ALLOC(f->cv[1].reserve(px));
+  hipStream_t s = stream_of(c, stream);
+  HIPCHK(f->order.begin(s));
   DenoisePrepareArgs pa;
   pa.rec = f->rec.p;
   pa.cv = f->cv[0].p;
@@ -1414,7 +1311,8 @@ int pt_film_denoise_device(pt_film* f, const pt_denoise_params* params, float* h
   fa.W = f->W;
   fa.H = f->H;
   HIPCHK(ptk_denoise_finish(&fa, s));
-  return film_end(f, s);
+  HIPCHK(f->order.end(s));
+  return PT_OK;
 }
 
 int pt_film_denoise(pt_film* f, const pt_denoise_params* params, float* hdr_host, uint32_t* rgba_host) {
@@ -1422,8 +1320,8 @@ int pt_film_denoise(pt_film* f, const pt_denoise_params* params, float* hdr_host
   pt_ctx* c = f->ctx;
   HIPCHK(hipSetDevice(c->device));
   const size_t px = (size_t)f->W * (size_t)f->H;
-  if (hdr_host) FILM_ALLOC(f->out_hdr.reserve(3 * px));
-  if (rgba_host) FILM_ALLOC(f->out_rgba.reserve(px));
+  if (hdr_host) HIPCHK_ALLOC(f->out_hdr.reserve(3 * px));
+  if (rgba_host) HIPCHK_ALLOC(f->out_rgba.reserve(px));
   if (int rc = pt_film_denoise_device(f, params, hdr_host ? f->out_hdr.p : nullptr,
                                       rgba_host ? f->out_rgba.p : nullptr, nullptr))
     return rc;
@@ -1461,11 +1359,10 @@ static int reproject_camera_check(const pt_camera& cam, const char* fn) {
 // when given.
 static int reproject_launch(pt_ctx* c, const pt_camera& old_cam, const uint4* rec, const float4* fo, const float4* fn,
                             int W, int H, const int32_t* types, int n_types, const pt_reproject_params& prm, uint4* out,
-                            unsigned long long* counts, hipEvent_t* ev, hipStream_t s) {
+                            unsigned long long* counts, const Event* ev, hipStream_t s) {
   std::vector<uint32_t> keep((size_t)n_types);
   reproject_keep_table(types, n_types, keep.data());
-  if (!c->ev_rp) HIPCHK(hipEventCreateWithFlags(&c->ev_rp, hipEventDisableTiming));
-  if (c->rp_ordered && c->rp_stream != s) HIPCHK(hipStreamWaitEvent(s, c->ev_rp, 0));
+  HIPCHK(c->rp_order.begin(s));
   if (int rc = sync_list(c->rp_keep, c->rp_keep_host, keep.data(), keep.size(), s)) return rc;
   ReprojectArgs a;
   std::memset(&a, 0, sizeof(a));
@@ -1486,9 +1383,7 @@ static int reproject_launch(pt_ctx* c, const pt_camera& old_cam, const uint4* re
   if (ev) HIPCHK(hipEventRecord(ev[0], s));
   HIPCHK(ptk_reproject(&a, s));
   if (ev) HIPCHK(hipEventRecord(ev[1], s));
-  HIPCHK(hipEventRecord(c->ev_rp, s));
-  c->rp_stream = s;
-  c->rp_ordered = true;
+  HIPCHK(c->rp_order.end(s));
   return PT_OK;
 }
 
@@ -1501,8 +1396,7 @@ int pt_reproject_device(pt_ctx* c, const pt_camera* old_cam, const void* rec_dev
   if (int rc = reproject_params(params, &prm, "pt_reproject_device")) return rc;
   if (!old_cam || !rec_dev || !feat_old_dev || !feat_new_dev || !rec_out_dev)
     return fail(PT_E_INVALID, "pt_reproject_device: NULL argument");
-  if (width < 1 || height < 1 || width > 65535 || height > 65535 || (int64_t)width * height > (int64_t)1 << 30)
-    return fail(PT_E_INVALID, "pt_reproject_device: width and height must be 1 .. 65535 and width * height <= 2^30");
+  if (int rc = check_frame_dims(width, height, "pt_reproject_device")) return rc;
   const size_t px = (size_t)width * (size_t)height;
   const uintptr_t a0 = (uintptr_t)rec_dev, b0 = (uintptr_t)rec_out_dev, len = 2 * px * sizeof(uint4);
   if (a0 < b0 + len && b0 < a0 + len)
@@ -1518,7 +1412,7 @@ int pt_reproject_device(pt_ctx* c, const pt_camera* old_cam, const void* rec_dev
   HIPCHK(hipSetDevice(c->device));
   return reproject_launch(c, *old_cam, (const uint4*)rec_dev, (const float4*)feat_old_dev, (const float4*)feat_new_dev,
                           width, height, bsdf_types_host, n_bsdfs, prm, (uint4*)rec_out_dev,
-                          (unsigned long long*)counts_dev, nullptr, stream ? (hipStream_t)stream : c->stream);
+                          (unsigned long long*)counts_dev, nullptr, stream_of(c, stream));
 }
 
 int pt_film_reproject(pt_film* f, const pt_reproject_params* params, void* stream) {
@@ -1538,13 +1432,12 @@ int pt_film_reproject(pt_film* f, const pt_reproject_params* params, void* strea
   std::vector<int4> tl;
   if ((rc = build_tiles(c, &whole, 1, tl))) return rc;
   const size_t px = (size_t)f->W * (size_t)f->H;
-  FILM_ALLOC(f->rec2.reserve(2 * px));
-  FILM_ALLOC(f->feat2.reserve(2 * px));
-  FILM_ALLOC(f->rp_counts.reserve(2));
-  for (hipEvent_t& e : f->ev_rp)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  if ((rc = film_begin(f, s))) return rc;
+  HIPCHK_ALLOC(f->rec2.reserve(2 * px));
+  HIPCHK_ALLOC(f->feat2.reserve(2 * px));
+  HIPCHK_ALLOC(f->rp_counts.reserve(2));
+  for (Event& e : f->ev_rp) HIPCHK(e.create());
+  hipStream_t s = stream_of(c, stream);
+  HIPCHK(f->order.begin(s));
   if ((rc = features_launch(c, tl, f->feat2.p, s))) return rc;  // (the whole frame: every record is written)
   if ((rc = reproject_launch(c, f->feat_cam, f->rec.p, f->feat.p, f->feat2.p, f->W, f->H, c->bsdf_types.data(),
                              (int)c->bsdf_types.size(), prm, f->rec2.p, f->rp_counts.p, f->ev_rp, s)))
@@ -1553,7 +1446,8 @@ int pt_film_reproject(pt_film* f, const pt_reproject_params* params, void* strea
   std::swap(f->rec, f->rec2);
   std::swap(f->feat, f->feat2);
   f->feat_cam = c->cam;
-  return film_end(f, s);
+  HIPCHK(f->order.end(s));
+  return PT_OK;
 }
 
 int pt_film_get_reproject_info(pt_film* f, pt_reproject_info* out) {
@@ -1587,7 +1481,7 @@ int pt_render_frames_device(pt_ctx* c, const pt_tile* tiles, int32_t n_tiles, in
   std::vector<int4> tl;
   if ((rc = build_tiles(c, tiles, n_tiles, tl))) return rc;
   if (int rc2 = check_packed(c, tiles, n_tiles, flags, "pt_render_frames_device")) return rc2;
-  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  hipStream_t s = stream_of(c, stream);
   // One launch for the batch in the plain common build; the environment-light
   // and global-table builds, diagnostics and PT_FRAME_BATCH=0 render the
   // frames one launch each (the same images)
@@ -1619,7 +1513,7 @@ static void tile_complete(const pt_ctx::TileBatch* b) {
     for (int y = j.t.y; y < j.t.y + j.t.w; ++y) {
       const size_t dst = ((size_t)y * (size_t)b->W + (size_t)j.t.x) * 3;
       const size_t src = ((size_t)(y - b->y0) * (size_t)b->W + (size_t)j.t.x) * 3;
-      std::memcpy(j.hdr + dst, b->stage + src, (size_t)j.t.z * 3 * sizeof(float));
+      std::memcpy(j.hdr + dst, b->stage.p + src, (size_t)j.t.z * 3 * sizeof(float));
     }
     if (j.rgba) (void)pt_to_color(j.hdr, b->W, b->H, j.t.x, j.t.y, j.t.x + j.t.z, j.t.y + j.t.w, j.rgba);
   }
@@ -1630,43 +1524,26 @@ static void tile_complete(const pt_ctx::TileBatch* b) {
 static void tile_worker(pt_ctx* c) {
   (void)hipSetDevice(c->device);
   for (;;) {
-    pt_ctx::TileBatch* b = nullptr;
+    std::unique_ptr<pt_ctx::TileBatch> b;
     {
       std::unique_lock<std::mutex> lk(c->tmu);
       c->tcv.wait(lk, [&] { return c->tstop || !c->tpending.empty(); });
       if (c->tpending.empty()) return;  // stopping, nothing left to complete
-      b = c->tpending.front();
+      b = std::move(c->tpending.front());
       c->tpending.pop_front();
     }
     const hipError_t e = hipEventSynchronize(b->ev);
-    if (e == hipSuccess) tile_complete(b);
+    if (e == hipSuccess) tile_complete(b.get());
     std::lock_guard<std::mutex> lk(c->tmu);
     if (e != hipSuccess && c->terr == PT_OK) {
       c->terr = PT_E_HIP;
       c->terrmsg = std::string("tile completion: ") + hipGetErrorString(e);
     }
     b->jobs.clear();
-    c->tfree.push_back(b);
+    c->tfree.push_back(std::move(b));
     --c->tinflight;
     c->tcv.notify_all();
   }
-}
-
-static void tile_worker_stop(pt_ctx* c) {
-  if (c->tworker.joinable()) {
-    {
-      std::lock_guard<std::mutex> lk(c->tmu);
-      c->tstop = true;
-    }
-    c->tcv.notify_all();
-    c->tworker.join();  // drains the pending batches first
-  }
-  for (auto* b : c->tfree) {
-    if (b->stage) (void)hipHostFree(b->stage);
-    if (b->ev) (void)hipEventDestroy(b->ev);
-    delete b;
-  }
-  c->tfree.clear();
 }
 
 // A batch that could not be launched: its tiles are dropped, so the failure is
@@ -1714,7 +1591,7 @@ static int tile_launch_impl(pt_ctx* c) {
     y1 = std::max(y1, t.y + t.w);
   }
   const size_t need = (size_t)(y1 - y0) * W * 3;
-  pt_ctx::TileBatch* b = nullptr;
+  std::unique_ptr<pt_ctx::TileBatch> b;
   {
     std::unique_lock<std::mutex> lk(c->tmu);
     if (!c->tworker.joinable()) {
@@ -1723,52 +1600,36 @@ static int tile_launch_impl(pt_ctx* c) {
     }
     c->tcv.wait(lk, [&] { return !c->tfree.empty() || c->tinflight < kMaxBatchesInFlight; });
     if (!c->tfree.empty()) {
-      b = c->tfree.back();
+      b = std::move(c->tfree.back());
       c->tfree.pop_back();
     }
   }
-  if (!b) b = new pt_ctx::TileBatch();
-  auto give_back = [&] {
-    std::lock_guard<std::mutex> lk(c->tmu);
-    c->tfree.push_back(b);
-  };
-  if (b->cap < need) {
-    if (b->stage) (void)hipHostFree(b->stage);
-    b->stage = nullptr;
-    b->cap = 0;
-    if (hipHostMalloc((void**)&b->stage, need * sizeof(float), hipHostMallocDefault) != hipSuccess) {
-      give_back();
-      return fail(PT_E_HIP, "pt_tile_submit: pinned staging allocation failed");
+  if (!b) b.reset(new pt_ctx::TileBatch());
+  // a batch that is not launched (any return before it is pending) goes back for reuse
+  struct GiveBack {
+    pt_ctx* c;
+    std::unique_ptr<pt_ctx::TileBatch>& b;
+    ~GiveBack() {
+      if (!b) return;
+      std::lock_guard<std::mutex> lk(c->tmu);
+      c->tfree.push_back(std::move(b));
     }
-    b->cap = need;
-  }
-  if (!b->ev && hipEventCreateWithFlags(&b->ev, hipEventDisableTiming) != hipSuccess) {
-    give_back();
-    return fail(PT_E_HIP, "pt_tile_submit: event creation failed");
-  }
-  if (hipError_t e = c->frame.reserve(W * H * 3); e != hipSuccess) {
-    give_back();
-    return fail(PT_E_HIP, std::string("pt_tile_submit: ") + hipGetErrorString(e));
-  }
+  } give_back{c, b};
+  HIPCHK(b->stage.reserve(need));
+  HIPCHK(b->ev.create(hipEventDisableTiming));
+  HIPCHK(c->frame.reserve(W * H * 3));
   float* fr = c->frame.p;
-  if (int rc = launch(c, tl, &fr, 1, nullptr, c->stream, 0)) {
-    give_back();
-    return rc;
-  }
-  hipError_t e = hipMemcpyAsync(b->stage, c->frame.p + (size_t)y0 * W * 3, need * sizeof(float),
-                                hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipEventRecord(b->ev, c->stream);
-  if (e != hipSuccess) {
-    give_back();
-    return fail(PT_E_HIP, std::string("pt_tile_submit: ") + hipGetErrorString(e));
-  }
+  if (int rc = launch(c, tl, &fr, 1, nullptr, c->stream, 0)) return rc;
+  HIPCHK(hipMemcpyAsync(b->stage.p, c->frame.p + (size_t)y0 * W * 3, need * sizeof(float), hipMemcpyDeviceToHost,
+                        c->stream));
+  HIPCHK(hipEventRecord(b->ev, c->stream));
   b->jobs = std::move(jobs);
   b->y0 = y0;
   b->W = (int)W;
   b->H = (int)H;
   {
     std::lock_guard<std::mutex> lk(c->tmu);
-    c->tpending.push_back(b);
+    c->tpending.push_back(std::move(b));
     ++c->tinflight;
   }
   c->tcv.notify_all();
@@ -1883,6 +1744,13 @@ int pt_debug_read_bvh(pt_ctx* c, void* nodes4, void* nodes2, void* prims, float*
   return PT_OK;
 }
 
+int pt_debug_live_resources(pt_resource_counts* out) {
+  if (!out) return fail(PT_E_INVALID, "pt_debug_live_resources: out is NULL");
+  const HipLiveCounts& n = hip_live();
+  *out = pt_resource_counts{n.device_arrays, n.device_bytes, n.pinned_arrays, n.events, n.streams};
+  return PT_OK;
+}
+
 // Host replay of the environment light's inverse-CDF searches (the kernel's
 // record_lower_bound over the tables build_env_tables makes) against
 // std::lower_bound, for n query pairs (u1, u2) in [0, 1): the row search over
@@ -1929,7 +1797,7 @@ int pt_get_launch_times(pt_ctx* c, float* kernel_ms, float* resolve_ms, int32_t 
   if (k == 0) return PT_OK;
   HIPCHK(hipSetDevice(c->device));
   for (int64_t i = 0; i < k; ++i) {
-    hipEvent_t* tri = c->ev[(c->n_launches - k + i) % pt_ctx::kRing];
+    const Event* tri = c->ev[(c->n_launches - k + i) % pt_ctx::kRing];
     HIPCHK(hipEventSynchronize(tri[2]));
     float ms = 0.f;
     HIPCHK(hipEventElapsedTime(&ms, tri[0], tri[1]));

@@ -155,8 +155,9 @@ __device__ __forceinline__ uint32_t pt_fastdiv(uint32_t u, uint32_t m, uint32_t 
   return m ? __umulhi(u, m) >> sh : u >> sh;
 }
 
-// GPU BVH build (lbvh.hip).  Inputs in upload order; outputs hipMalloc'd by
-// the builder (the caller owns and frees them).
+// GPU BVH build (lbvh.hip).  Inputs in upload order; outputs allocated by
+// the builder and handed out on success only (the caller adopts them into
+// DevBufs, hip_owned.h); after a failure `out` holds nothing.
 struct LbvhIn {
   int n;
   const DPrim* prims;    // device, input order

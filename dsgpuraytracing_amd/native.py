@@ -121,6 +121,11 @@ class pt_bvh_info(ctypes.Structure):
                 ("has_prim_map", c_int32), ("root_lo", c_float * 3), ("root_hi", c_float * 3)]
 
 
+class pt_resource_counts(ctypes.Structure):
+    _fields_ = [("device_arrays", c_int64), ("device_bytes", c_int64), ("pinned_arrays", c_int64),
+                ("events", c_int64), ("streams", c_int64)]
+
+
 PT_FILM_LUM_FLOOR = 1e-3 # floor of the film's relative error (include/ptgpu.h), as a float32 in the arithmetic
 
 # Every symbol include/ptgpu.h and include/ptgpu_scene.h declare, with ctypes signatures.
@@ -144,6 +149,7 @@ _SIGS = {
     "pt_get_wave_trace": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
     "pt_debug_bvh_info": (c_int32, [c_void_p, POINTER(pt_bvh_info)]),
     "pt_debug_read_bvh": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "pt_debug_live_resources": (c_int32, [POINTER(pt_resource_counts)]),
     "pt_last_error": (c_char_p, []),
     "pt_to_color": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "pt_to_color_check": (c_int64, [c_uint32, c_uint32]),

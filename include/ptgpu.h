@@ -382,6 +382,21 @@ int pt_debug_bvh_info(pt_ctx* ctx, pt_bvh_info* out);
  *   norms: n_prims x 9 floats (the three vertex normals; 0 for spheres).
  *   prim_map: n_prims int32, position in `prims` -> the caller's index. */
 int pt_debug_read_bvh(pt_ctx* ctx, void* nodes4, void* nodes2, void* prims, float* norms, int32_t* prim_map);
+/* Diagnostics: the HIP resources this library holds at the moment, in the
+ * whole process (every context and film, and a GPU tree build in progress):
+ * device arrays and their bytes, pinned host arrays, events and streams.
+ * Each is owned by one object and counted where it is acquired and released,
+ * so a context's pt_destroy brings every count back to its value before that
+ * context's pt_create.  Needs no context and no device; PT_E_INVALID for a
+ * NULL argument. */
+typedef struct pt_resource_counts {
+  int64_t device_arrays;
+  int64_t device_bytes;
+  int64_t pinned_arrays;
+  int64_t events;
+  int64_t streams;
+} pt_resource_counts;
+int pt_debug_live_resources(pt_resource_counts* out);
 const char* pt_last_error(void);
 
 /* Output row, host side (no device needed):
