@@ -1,10 +1,11 @@
 """Builds the in-tree native library ``libptgpu.so`` for gfx950 with hipcc.
 
 The library holds the HIP kernels (csrc/pt_kernels.hip), the C ABI
-(csrc/pt_api.cpp, include/ptgpu.h), the host flattening of an uploaded scene
-(csrc/scene_flatten.cpp) and the native host scene pipeline
-(csrc/scene_host.cpp).  Only pt_api.cpp and the .hip files are compiled as
-HIP; every other .cpp is plain C++.  It is built in-tree so that it travels with the
+(csrc/pt_api.cpp and csrc/pt_api_film.cpp over the context of csrc/pt_ctx.h;
+include/ptgpu.h), the asynchronous tile seam (csrc/tile_seam.cpp), the host
+flattening of an uploaded scene (csrc/scene_flatten.cpp) and the native host
+scene pipeline (csrc/scene_host.cpp).  Only the pt_api*.cpp units and the .hip
+files are compiled as HIP; every other .cpp is plain C++.  It is built in-tree so that it travels with the
 repository snapshot to the GPU box; nothing is installed.
 """
 from __future__ import annotations

@@ -1,7 +1,9 @@
 // hip_owned.h — every HIP resource of the host code is owned by one of these
 // types and released by its destructor: device arrays (DevBuf), pinned host
-// arrays (PinnedBuf), events, streams, and the ordering of consecutive
-// operations that may come on different streams (StreamOrder).  No kernels;
+// arrays (PinnedBuf), events, streams, a device list with the host mirror of
+// what it holds (DevList), a timed pair of events (TimedSpan), and the ordering
+// of consecutive operations that may come on different streams (StreamOrder).
+// No kernels;
 // only <hip/hip_runtime.h> types and calls.  The live objects of each kind are
 // counted process-wide, here and nowhere else (pt_debug_live_resources).
 #pragma once
@@ -10,7 +12,9 @@
 #include <algorithm>
 #include <atomic>
 #include <cstddef>
+#include <cstring>
 #include <utility>
+#include <vector>
 
 struct HipLiveCounts {
   std::atomic<long long> device_arrays{0}, device_bytes{0}, pinned_arrays{0}, events{0}, streams{0};
@@ -60,6 +64,28 @@ struct DevBuf {
 };
 template <class T>
 void swap(DevBuf<T>& a, DevBuf<T>& b) noexcept { a.swap(b); }
+
+// A device list with a host mirror of what it holds: uploaded (on `s`) only
+// when it changed -- the lists rarely change between frames.  Never a null
+// device list: an empty one (a launch may cull every block) still has an array.
+template <class D, class T = D>
+struct DevList {
+  static_assert(sizeof(D) == sizeof(T), "the list uploads without conversion");
+  DevBuf<D> dev;
+  std::vector<T> host;  // what `dev` holds
+  hipError_t sync(const T* list, size_t n, hipStream_t s) {
+    const D* held = dev.p;
+    const hipError_t r = dev.reserve(n);
+    if (dev.p != held) host.clear();  // (a new array holds nothing yet)
+    if (r != hipSuccess) return r;
+    if (n == host.size() && (n == 0 || std::memcmp(list, host.data(), n * sizeof(T)) == 0)) return hipSuccess;
+    host.assign(list, list + n);  // (the copy's source outlives the call)
+    if (n == 0) return hipSuccess;
+    const hipError_t e = hipMemcpyAsync(dev.p, host.data(), n * sizeof(T), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) host.clear();  // (not what the device holds)
+    return e;
+  }
+};
 
 template <class T>
 struct PinnedBuf {  // hipHostMalloc'd; grows only
@@ -118,6 +144,31 @@ struct Stream {
     return r;
   }
   operator hipStream_t() const { return s; }
+};
+
+// The device time between two points of a stream, read when asked for.
+struct TimedSpan {
+  Event ev[2];
+  bool timed = false;  // begin() and end() were recorded
+  hipError_t create() {
+    const hipError_t e = ev[0].create();
+    return e == hipSuccess ? ev[1].create() : e;
+  }
+  hipError_t begin(hipStream_t s) {
+    const hipError_t e = create();
+    return e == hipSuccess ? hipEventRecord(ev[0], s) : e;
+  }
+  hipError_t end(hipStream_t s) {
+    const hipError_t e = hipEventRecord(ev[1], s);
+    if (e == hipSuccess) timed = true;
+    return e;
+  }
+  // Waits for the end; nothing timed yet: *out is left as it is.
+  hipError_t ms(float* out) const {
+    if (!timed) return hipSuccess;
+    const hipError_t e = hipEventSynchronize(ev[1]);
+    return e == hipSuccess ? hipEventElapsedTime(out, ev[0], ev[1]) : e;
+  }
 };
 
 // Consecutive operations on one object are ordered: one that comes on another

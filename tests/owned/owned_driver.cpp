@@ -1,14 +1,19 @@
-// Stand-alone check of csrc/hip_owned.h (tests/test_hip_owned.py) against the
-// fake HIP of tests/owned/fake_hip: built with AddressSanitizer +
+// Stand-alone check of csrc/hip_owned.h and csrc/tile_seam.cpp
+// (tests/test_hip_owned.py) against the fake HIP of tests/owned/fake_hip,
+// where the seam's renders are copies the driver makes: built with AddressSanitizer +
 // UndefinedBehaviorSanitizer, leaks detected.  Every CHECK that fails prints its
 // line and the program exits 1; "owned ok" at the end.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <thread>
 #include <utility>
 
+#include "../../include/ptgpu.h"
 #include "hip_owned.h"
+#include "tile_seam.h"
 
 #define CHECK(x)                                                  \
   do {                                                            \
@@ -189,6 +194,195 @@ static void test_event_stream_order() {
   counts_agree(0, 0);
 }
 
+static void test_dev_list() {
+  {
+    Stream s;
+    CHECK(s.create(hipStreamNonBlocking) == hipSuccess);
+    DevList<int> l;
+    int a[6] = {1, 2, 3, 4, 5, 6};
+    fake.copies = 0;
+    CHECK(l.sync(a, 0, s) == hipSuccess && l.dev.p && fake.copies == 0);  // an empty list still has an array
+    CHECK(l.sync(a, 4, s) == hipSuccess && l.dev.n == 4 && fake.copies == 1 && std::memcmp(l.dev.p, a, 16) == 0);
+    const int* held = l.dev.p;
+    CHECK(l.sync(a, 4, s) == hipSuccess && fake.copies == 1 && l.dev.p == held);  // equal contents: no upload
+    a[2] = 9;
+    CHECK(l.sync(a, 4, s) == hipSuccess && fake.copies == 2 && l.dev.p[2] == 9);
+    CHECK(l.sync(a, 2, s) == hipSuccess && fake.copies == 3 && l.dev.p == held && l.host.size() == 2);  // shorter: the same array
+    a[0] = 7;  // the mirror is the copy's source, not the caller's list
+    CHECK(l.host[0] == 1 && l.dev.p[0] == 1);
+    CHECK(l.sync(a, 6, s) == hipSuccess && fake.copies == 4 && l.dev.p != held && std::memcmp(l.dev.p, a, 24) == 0);  // grown
+    counts_agree(1, 24);
+    // a failed copy: the mirror is not what the device holds, so the same list uploads again
+    a[5] = 8;
+    fake.copy_fail_at = 1;
+    CHECK(l.sync(a, 6, s) == hipErrorInvalidValue && l.host.empty());
+    CHECK(l.sync(a, 6, s) == hipSuccess && fake.copies == 6 && l.dev.p[5] == 8);
+    // a failed growth leaves no array and no mirror; the next array is new and
+    // holds nothing yet, so the list the mirror held before uploads again
+    fake.fail_at = 1;
+    CHECK(l.sync(a, 7, s) == hipErrorOutOfMemory && !l.dev.p && l.host.empty() && fake.copies == 6);
+    CHECK(l.sync(a, 6, s) == hipSuccess && fake.copies == 7 && std::memcmp(l.dev.p, a, 24) == 0);
+    // so does it when the array was replaced behind the list
+    l.dev.release();
+    CHECK(l.sync(a, 6, s) == hipSuccess && fake.copies == 8 && std::memcmp(l.dev.p, a, 24) == 0);
+    // a list of another type of the same size uploads without conversion
+    struct Rect {
+      int x, y, w, h;
+    };
+    DevList<int4, Rect> r;
+    const Rect rect[2] = {{1, 2, 3, 4}, {5, 6, 7, 8}};
+    CHECK(r.sync(rect, 2, s) == hipSuccess && r.dev.p[1].x == 5 && r.dev.p[1].w == 8);
+  }
+  counts_agree(0, 0);
+}
+
+static void test_timed_span() {
+  {
+    Stream s;
+    CHECK(s.create(hipStreamNonBlocking) == hipSuccess);
+    TimedSpan t;
+    float ms = -1.f;
+    CHECK(t.ms(&ms) == hipSuccess && ms == -1.f && fake.events == 0);  // nothing timed: left as it is
+    CHECK(t.create() == hipSuccess && t.create() == hipSuccess && fake.events == 2);
+    fake.log.clear();
+    CHECK(t.begin(s) == hipSuccess && !t.timed && fake.events == 2);
+    CHECK(t.ms(&ms) == hipSuccess && ms == -1.f);
+    CHECK(t.end(s) == hipSuccess && t.timed && fake.log.size() == 2);
+    const size_t syncs = fake_evsyncs();
+    CHECK(t.ms(&ms) == hipSuccess && ms == 1.5f && fake_evsyncs() == syncs + 1);  // waits for the end (the fake clock: 1.5 per record)
+    CHECK(fake.evsyncs.back() == ((hipEvent_t)t.ev[1])->id);
+    fake.evsync_fail_at = 1;
+    CHECK(t.ms(&ms) == hipErrorInvalidValue);
+    TimedSpan lazy;  // begin() makes the events where create() was not called
+    CHECK(lazy.begin(s) == hipSuccess && lazy.end(s) == hipSuccess && fake.events == 4);
+  }
+  CHECK(fake.events == 0);
+}
+
+// ---- the tile seam.  A "render" here: rows [y0, y0 + rows) of a W-wide frame
+// filled with `value` in the batch's stage, and the batch's event recorded.
+static int n_to_color = 0;
+extern "C" int pt_to_color(const float*, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, uint32_t*) {
+  return ++n_to_color, PT_OK;  // (on the completion thread; read after drain())
+}
+
+constexpr int kW = 4, kRows = 2;
+
+static TileBatch* launch_batch(TileSeam& seam, hipStream_t s, float* hdr, int y0, float value, uint32_t* rgba = nullptr) {
+  std::unique_ptr<TileBatch> b = seam.acquire();
+  CHECK(b && b->jobs.empty());
+  CHECK(b->stage.reserve(kW * kRows * 3) == hipSuccess && b->ev.create(hipEventDisableTiming) == hipSuccess);
+  std::fill(b->stage.p, b->stage.p + kW * kRows * 3, value);
+  CHECK(hipEventRecord(b->ev, s) == hipSuccess);
+  b->jobs.push_back(TileJob{make_int4(1, y0, 2, kRows), hdr, rgba});  // columns 1 and 2 of the rows
+  b->y0 = y0, b->W = kW, b->H = 64;
+  TileBatch* raw = b.get();
+  seam.submit(std::move(b));
+  return raw;
+}
+
+// rows [y0, y0 + kRows): columns 1 and 2 hold `value`, the others are untouched (-1)
+static bool rows_hold(const std::vector<float>& hdr, int y0, float value) {
+  for (int y = y0; y < y0 + kRows; ++y)
+    for (int x = 0; x < kW; ++x)
+      for (int ch = 0; ch < 3; ++ch)
+        if (hdr[((size_t)y * kW + x) * 3 + ch] != (x == 1 || x == 2 ? value : -1.f)) return false;
+  return true;
+}
+
+static void test_seam_queue_and_faults() {
+  setenv("PT_TILE_BATCH", "2", 1);
+  setenv("PT_FAULT_TILE_LAUNCH", "2", 1);
+  TileSeam seam(0);
+  unsetenv("PT_TILE_BATCH");
+  unsetenv("PT_FAULT_TILE_LAUNCH");
+  CHECK(!seam.queued());
+  CHECK(!seam.push(TileJob{make_int4(0, 0, 1, 1), nullptr, nullptr}) && seam.queued());
+  CHECK(seam.push(TileJob{make_int4(1, 0, 1, 1), nullptr, nullptr}));  // a full batch
+  const std::vector<TileJob> jobs = seam.take_queue();
+  CHECK(jobs.size() == 2 && jobs[1].t.x == 1 && !seam.queued());
+  CHECK(!seam.fault_injected() && seam.fault_injected() && !seam.fault_injected());  // the second launch only
+  std::string msg = "?";
+  CHECK(seam.drain(&msg) == PT_OK && msg.empty());  // nothing submitted: nothing to wait for, no thread
+  CHECK(seam.record_failure(PT_E_INVALID, "first") == PT_E_INVALID && seam.record_failure(PT_E_HIP, "second") == PT_E_HIP);
+  CHECK(seam.drain(&msg) == PT_E_INVALID && msg == "first");  // the first error, once
+  CHECK(seam.drain(&msg) == PT_OK && msg.empty());
+}
+
+static void test_seam_completion() {
+  std::vector<float> hdr(64 * kW * 3, -1.f);
+  std::string msg;
+  std::atomic<bool> destroying{false};
+  std::thread opener;
+  {
+    Stream s;
+    CHECK(s.create(hipStreamNonBlocking) == hipSuccess);
+    TileSeam seam(0);
+    // batches complete in launch order, each after its own event
+    fake.gate = true;
+    fake.evsyncs.clear();
+    std::vector<int> ids;
+    uint32_t rgba = 0;
+    for (int k = 0; k < 3; ++k) ids.push_back(((hipEvent_t)launch_batch(seam, s, hdr.data(), 2 * k, (float)k, k == 1 ? &rgba : nullptr)->ev)->id);
+    CHECK(fake_evsyncs() == 0);
+    fake_permit(3);
+    CHECK(seam.drain(&msg) == PT_OK && msg.empty());
+    CHECK(fake.evsyncs == ids && ids[0] != ids[1] && ids[1] != ids[2]);
+    for (int k = 0; k < 3; ++k) CHECK(rows_hold(hdr, 2 * k, (float)k));
+    CHECK(n_to_color == 1);  // the one job with a frameBuffer
+    CHECK(fake.pinned == 3 && fake.events == 3);  // kept for reuse
+
+    // with kMaxBatchesInFlight in flight and none free, acquire waits until one completes
+    std::vector<std::unique_ptr<TileBatch>> taken;  // (the three free ones, out of the way)
+    for (int k = 0; k < 3; ++k) taken.push_back(seam.acquire());
+    fake.evsyncs.clear();
+    TileBatch* first = nullptr;
+    for (int k = 0; k < TileSeam::kMaxBatchesInFlight; ++k) {
+      TileBatch* b = launch_batch(seam, s, hdr.data(), 2 * k, 10.f + k);
+      if (k == 0) first = b;
+    }
+    CHECK(fake.pinned == 3 + TileSeam::kMaxBatchesInFlight);
+    std::atomic<bool> entering{false};
+    std::thread helper([&] {
+      while (!entering) std::this_thread::yield();
+      fake_permit(1);
+    });
+    entering = true;
+    std::unique_ptr<TileBatch> ninth = seam.acquire();
+    CHECK(fake_evsyncs() >= 1 && ninth.get() == first && rows_hold(hdr, 0, 10.f));  // the completed one, reused
+    CHECK(fake.pinned == 3 + TileSeam::kMaxBatchesInFlight);
+    helper.join();
+    seam.give_back(std::move(ninth));
+    for (auto& b : taken) seam.give_back(std::move(b));
+    fake_permit(TileSeam::kMaxBatchesInFlight - 1);
+    CHECK(seam.drain(&msg) == PT_OK);
+    for (int k = 0; k < TileSeam::kMaxBatchesInFlight; ++k) CHECK(rows_hold(hdr, 2 * k, 10.f + k));
+    fake.gate = false;
+
+    // a failed synchronise: its tiles are not copied; drain reports it once
+    fake.evsync_fail_at = 2;
+    launch_batch(seam, s, hdr.data(), 20, 30.f);
+    launch_batch(seam, s, hdr.data(), 22, 31.f);
+    launch_batch(seam, s, hdr.data(), 24, 32.f);
+    CHECK(seam.drain(&msg) == PT_E_HIP && msg == "tile completion: fake error");
+    CHECK(rows_hold(hdr, 20, 30.f) && rows_hold(hdr, 22, -1.f) && rows_hold(hdr, 24, 32.f));
+    CHECK(seam.drain(&msg) == PT_OK && msg.empty());
+
+    // destruction with batches pending completes them
+    fake.gate = true;
+    for (int k = 0; k < 3; ++k) launch_batch(seam, s, hdr.data(), 30 + 2 * k, 40.f + k);
+    opener = std::thread([&] {
+      while (!destroying) std::this_thread::yield();
+      fake_permit(3);
+    });
+    destroying = true;
+  }  // (the seam's destructor returns once the gate was opened and the three are complete)
+  opener.join();
+  fake.gate = false;
+  for (int k = 0; k < 3; ++k) CHECK(rows_hold(hdr, 30 + 2 * k, 40.f + k));
+  CHECK(fake.pinned == 0 && fake.events == 0 && fake.streams == 0);
+}
+
 int main() {
   counts_agree(0, 0);
   test_reserve();
@@ -200,6 +394,10 @@ int main() {
   test_pinned();
   counts_agree(0, 0);
   test_event_stream_order();
+  test_dev_list();
+  test_timed_span();
+  test_seam_queue_and_faults();
+  test_seam_completion();
   CHECK(fake.dev == 0 && fake.pinned == 0 && fake.events == 0 && fake.streams == 0);
   std::printf("owned ok\n");
   return 0;

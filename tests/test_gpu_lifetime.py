@@ -251,6 +251,43 @@ def test_small_launches_open_render_slots_2_and_3(scene, monkeypatch):
     assert live() == before
 
 
+def test_slot_lists_grow_between_launches(scene, monkeypatch):
+    """Three device renders in one context, all on render slot 0
+    (PT_PIPELINE=0): 4 tiles, then 16 -- the slot's tile and block-start lists
+    grow into new arrays, which hold nothing of what their mirrors held --
+    then the 4 again.  Each frame is bit-identical to the same call in a fresh
+    context.  2 spp, depth 2."""
+    import torch
+    monkeypatch.delenv("PT_BVH_BUILD", raising=False)
+    monkeypatch.setenv("PT_PIPELINE", "0")
+    lists = [tile_fifo(W, H), tile_fifo(W, H, 16), tile_fifo(W, H)]
+    assert [len(t) for t in lists] == [4, 16, 4]
+
+    def context():
+        dev = Device(0)
+        dev.upload_scene(scene)
+        dev.set_camera(scene.camera)
+        dev.set_params(W, H, 2, 2, 1, 3)
+        return dev
+
+    def frame(dev, tiles):
+        out = torch.zeros(H * W * 3, dtype=torch.float32, device="cuda:0")
+        dev.render_tiles_device(tiles, out.data_ptr(), out_floats=out.numel())
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    before = live()
+    dev = context()
+    got = [frame(dev, t) for t in lists]
+    for tiles, img in zip(lists, got):
+        fresh = context()
+        want = frame(fresh, tiles)
+        fresh.close()
+        assert np.isfinite(want).all() and want.mean() > 0 and np.array_equal(img, want)
+    dev.close()
+    assert live() == before
+
+
 def test_refused_calls_change_nothing(scene, monkeypatch):
     monkeypatch.delenv("PT_BVH_BUILD", raising=False)
     L = native.lib()

@@ -1,10 +1,12 @@
-"""The owning types of csrc/hip_owned.h (DevBuf, PinnedBuf, Event, Stream,
-StreamOrder and their live counts) on the CPU.
+"""The owning types of csrc/hip_owned.h (DevBuf, DevList, PinnedBuf, Event,
+Stream, TimedSpan, StreamOrder and their live counts) and the tile seam of
+csrc/tile_seam.cpp (its queue, its lock and its completion thread) on the CPU.
 
 tests/owned/owned_driver.cpp includes the header against a fake HIP
 (tests/owned/fake_hip/hip/hip_runtime.h: malloc / free, counted dummy handles,
-logged synchronise / wait / record calls, a switch that fails the k-th
-allocation), is built with -fsanitize=address,undefined (no recovery) and run
+logged synchronise / wait / record calls, switches that fail the k-th
+allocation, copy or event synchronise, a gate that holds event synchronises),
+is built together with tile_seam.cpp with -fsanitize=address,undefined (no recovery) and run
 as a child process with leak detection: a failed assertion of the driver, a
 sanitizer report or a leak fails the test."""
 import os
@@ -25,7 +27,8 @@ def test_owned_types_under_sanitizers(tmp_path):
         pytest.skip("no g++")
     exe = str(tmp_path / "owned_driver")
     cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror"] + SAN + \
-        [f"-I{ROOT}/tests/owned/fake_hip", f"-I{CSRC}", os.path.join(ROOT, "tests", "owned", "owned_driver.cpp"), "-o", exe]
+        [f"-I{ROOT}/tests/owned/fake_hip", f"-I{CSRC}", os.path.join(ROOT, "tests", "owned", "owned_driver.cpp"),
+         os.path.join(CSRC, "tile_seam.cpp"), "-pthread", "-o", exe]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0",

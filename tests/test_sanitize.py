@@ -10,7 +10,7 @@ copies (truncations at many offsets, byte flips): any sanitizer report fails
 the test; ordinary error returns on corrupted input are expected.  The
 upload's host side (csrc/scene_flatten.cpp: primitive conversion, tree
 collapse, tables) has its own sanitized driver, tests/test_scene_flatten.py;
-what is left in the HIP translation units (pt_api.cpp, the kernels) is covered
+what is left in the HIP translation units (pt_api*.cpp, the kernels) is covered
 on the GPU box by tools/sanitize_gpu.sh (host-side -fsanitize after -Xarch_host)."""
 import os
 import shutil
