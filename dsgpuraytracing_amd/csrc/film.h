@@ -5,7 +5,7 @@
 //   rec[p]       = {sum.r, sum.g, sum.b, n}   f32 f32 f32 u32
 //   rec[W*H + p] = {mu, M2, k, pad}           f32 f32 u32 u32
 // all zero when clear.  The arithmetic is defined in include/ptgpu.h
-// (pt_film_add_pass / pt_film_resolve_device).
+// (pt_film_add_pass / pt_film_resolve_device / pt_film_merge_device).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,6 +36,13 @@ struct FilmErrArgs {
   int W, H;
 };
 
+struct FilmMergeArgs {
+  uint4* rec;                  // the film's 2 * W * H records: a, and the result
+  const uint4* in;             // the incoming 2 * W * H records: b (no overlap with rec)
+  unsigned long long* counts;  // merged, taken, empty, refused: added to
+  int W, H;
+};
+
 struct ToColorArgs {
   const float* hdr;
   const uint32_t* thr;
@@ -47,4 +54,5 @@ struct ToColorArgs {
 extern "C" hipError_t ptk_film_accumulate(const FilmAccArgs* a, int n_tiles, hipStream_t s);
 extern "C" hipError_t ptk_film_resolve(const FilmResolveArgs* a, hipStream_t s);
 extern "C" hipError_t ptk_film_tile_error(const FilmErrArgs* a, int n_tiles, hipStream_t s);
+extern "C" hipError_t ptk_film_merge(const FilmMergeArgs* a, hipStream_t s);
 extern "C" hipError_t ptk_to_color(const ToColorArgs* a, hipStream_t s);

@@ -1,7 +1,8 @@
 // film.hip — the device-resident progressive film: accumulate a pass, resolve
 // to the HDR mean / the RGBA8 toColor codes / the per-pixel error, and the
-// per-tile maximum of that error (include/ptgpu.h: pt_film_*), plus
-// pt_to_color_device, which shares the resolve's tonemap.
+// per-tile maximum of that error, and the merge of another film's records into
+// it (include/ptgpu.h: pt_film_*), plus pt_to_color_device, which shares the
+// resolve's tonemap.
 //
 // The film arithmetic is a definition (ptgpu.h), restated in numpy by
 // tests/film_helpers.py and compared bit for bit: every operation is one
@@ -121,6 +122,74 @@ __global__ __launch_bounds__(256) void film_tile_error_kernel(FilmErrArgs a) {
   if (threadIdx.x == 0) a.out[blockIdx.x] = fmaxf(fmaxf(s_max[0], s_max[1]), fmaxf(s_max[2], s_max[3]));
 }
 
+// pt_film_merge_device: film <- film (+) incoming records, the pairwise
+// combine of two Welford states (Chan et al.) as ptgpu.h defines it.  Whole
+// frame, the resolve's shape; each lane four rows.  A pixel's four records
+// are loaded together; only a taken or merged pixel stores.  The four class
+// counts are reduced per wave by ballot and popcount, the four waves through
+// LDS, and added to the device counter by one four-lane vector atomic per
+// workgroup (as reproject.hip counts kept and reset).
+__global__ __launch_bounds__(256) void film_merge_kernel(FilmMergeArgs a) {
+  __shared__ uint32_t s_cnt[4][4];
+  const int tx = (a.W + 31) >> 5;
+  const int x = (((int)blockIdx.x % tx) << 5) + ((int)threadIdx.x & 31);
+  const int y0 = (((int)blockIdx.x / tx) << 5) + ((int)threadIdx.x >> 5);
+  const size_t plane = (size_t)a.W * (size_t)a.H;
+  uint32_t n_cls[4] = {0, 0, 0, 0};  // merged, taken, empty, refused of the wave (uniform)
+  // (every lane takes every trip: the ballots below are whole-wave)
+#pragma unroll 1
+  for (int i = 0; i < 4; ++i) {
+    const int y = y0 + 8 * i;
+    const bool in_frame = x < a.W && y < a.H;
+    int cls = -1;
+    if (in_frame) {
+      const size_t p = (size_t)x + (size_t)y * (size_t)a.W;
+      const uint4 sb = a.in[p];
+      const uint4 eb = a.in[plane + p];
+      uint4 s = a.rec[p];
+      uint4 e = a.rec[plane + p];
+      const uint32_t n = s.w + sb.w;
+      if (sb.w == 0u) {
+        cls = 2;
+      } else if (s.w == 0u) {
+        cls = 1;
+        s = sb;
+        e = eb;
+      } else if (n < s.w) {  // n_a + n_b does not fit in 32 bits
+        cls = 3;
+      } else {
+        cls = 0;
+        const float na = (float)s.w, nb = (float)sb.w;
+        const float Wn = (float)n;
+        s.x = __float_as_uint(__uint_as_float(s.x) + __uint_as_float(sb.x));
+        s.y = __float_as_uint(__uint_as_float(s.y) + __uint_as_float(sb.y));
+        s.z = __float_as_uint(__uint_as_float(s.z) + __uint_as_float(sb.z));
+        s.w = n;
+        const float mu_a = __uint_as_float(e.x);
+        const float d = __uint_as_float(eb.x) - mu_a;
+        e.x = __float_as_uint(mu_a + d * (nb / Wn));
+        e.y = __float_as_uint((__uint_as_float(e.y) + __uint_as_float(eb.y)) + (d * d) * ((na * nb) / Wn));
+        e.z += eb.z;
+      }
+      if (cls < 2) {
+        a.rec[p] = s;
+        a.rec[plane + p] = e;
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c) n_cls[c] += (uint32_t)__popcll(__ballot(cls == c));
+  }
+  if (((int)threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) s_cnt[threadIdx.x >> 6][c] = n_cls[c];
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const uint32_t v = (s_cnt[0][threadIdx.x] + s_cnt[1][threadIdx.x]) + (s_cnt[2][threadIdx.x] + s_cnt[3][threadIdx.x]);
+    if (v) atomicAdd(a.counts + threadIdx.x, (unsigned long long)v);
+  }
+}
+
 // pt_to_color_device: one workgroup per 32x32 block of the rectangle.
 __global__ __launch_bounds__(256) void to_color_kernel(ToColorArgs a) {
   __shared__ uint32_t s_thr[256];
@@ -155,6 +224,12 @@ extern "C" hipError_t ptk_film_resolve(const FilmResolveArgs* a, hipStream_t s) 
 extern "C" hipError_t ptk_film_tile_error(const FilmErrArgs* a, int n_tiles, hipStream_t s) {
   if (n_tiles <= 0) return hipSuccess;
   hipLaunchKernelGGL(ptk::film_tile_error_kernel, dim3(n_tiles), dim3(256), 0, s, *a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t ptk_film_merge(const FilmMergeArgs* a, hipStream_t s) {
+  const int grid = ((a->W + 31) / 32) * ((a->H + 31) / 32);
+  hipLaunchKernelGGL(ptk::film_merge_kernel, dim3(grid), dim3(256), 0, s, *a);
   return hipGetLastError();
 }
 

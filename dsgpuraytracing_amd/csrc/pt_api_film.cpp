@@ -245,6 +245,100 @@ int pt_film_get_info(pt_film* f, pt_film_info* out) {
   return PT_OK;
 }
 
+// ---- the film's records out and in (ptgpu.h: pt_film_export*, pt_film_merge*; kernel: film.hip film_merge_kernel)
+static size_t film_rec_bytes(const pt_film* f) { return 2 * (size_t)f->W * (size_t)f->H * sizeof(uint4); }
+
+// True when the 2*W*H records at `p` share a byte with the film's own.
+static bool overlaps_film(const pt_film* f, const void* p) {
+  const uintptr_t a0 = (uintptr_t)f->rec.p, b0 = (uintptr_t)p, len = film_rec_bytes(f);
+  return a0 < b0 + len && b0 < a0 + len;
+}
+
+int pt_film_export_device(pt_film* f, void* rec_out_dev, void* stream) {
+  if (!f || !rec_out_dev) return fail(PT_E_INVALID, "pt_film_export_device: NULL argument");
+  if (overlaps_film(f, rec_out_dev))
+    return fail(PT_E_INVALID, "pt_film_export_device: the output overlaps the film's own records");
+  pt_ctx* c = f->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream_of(c, stream);
+  HIPCHK(f->order.begin(s));
+  HIPCHK(hipMemcpyAsync(rec_out_dev, f->rec.p, film_rec_bytes(f), hipMemcpyDeviceToDevice, s));
+  HIPCHK(f->order.end(s));
+  return PT_OK;
+}
+
+int pt_film_export(pt_film* f, void* rec_out_host) {
+  if (!f || !rec_out_host) return fail(PT_E_INVALID, "pt_film_export: NULL argument");
+  pt_ctx* c = f->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  HIPCHK(f->order.begin(s));
+  HIPCHK(hipMemcpyAsync(rec_out_host, f->rec.p, film_rec_bytes(f), hipMemcpyDeviceToHost, s));
+  HIPCHK(f->order.end(s));
+  HIPCHK(hipStreamSynchronize(s));
+  return PT_OK;
+}
+
+int pt_film_merge_device(pt_film* f, const void* rec_dev, void* stream) {
+  if (!f || !rec_dev) return fail(PT_E_INVALID, "pt_film_merge_device: NULL argument");
+  if (overlaps_film(f, rec_dev))
+    return fail(PT_E_INVALID, "pt_film_merge_device: the incoming records overlap the film's own");
+  pt_ctx* c = f->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK_ALLOC(f->mg_counts.reserve(4));
+  HIPCHK(f->t_mg.create());
+  hipStream_t s = stream_of(c, stream);
+  HIPCHK(f->order.begin(s));
+  FilmMergeArgs a;
+  a.rec = f->rec.p;
+  a.in = (const uint4*)rec_dev;
+  a.counts = f->mg_counts.p;
+  a.W = f->W;
+  a.H = f->H;
+  HIPCHK(hipMemsetAsync(f->mg_counts.p, 0, 4 * sizeof(unsigned long long), s));
+  HIPCHK(f->t_mg.begin(s));
+  HIPCHK(ptk_film_merge(&a, s));
+  HIPCHK(f->t_mg.end(s));
+  HIPCHK(f->order.end(s));
+  return PT_OK;
+}
+
+int pt_film_merge(pt_film* f, const void* rec_host) {
+  if (!f || !rec_host) return fail(PT_E_INVALID, "pt_film_merge: NULL argument");
+  pt_ctx* c = f->ctx;
+  HIPCHK(hipSetDevice(c->device));
+  HIPCHK_ALLOC(f->mg_stage.reserve(2 * (size_t)f->W * (size_t)f->H));
+  hipStream_t s = c->stream;
+  // (the staging buffer is free: the merge that last read it was waited for below)
+  HIPCHK(hipMemcpyAsync(f->mg_stage.p, rec_host, film_rec_bytes(f), hipMemcpyHostToDevice, s));
+  if (int rc = pt_film_merge_device(f, f->mg_stage.p, nullptr)) return rc;
+  HIPCHK(hipStreamSynchronize(s));
+  return PT_OK;
+}
+
+int pt_film_get_merge_info(pt_film* f, pt_film_merge_info* out) {
+  if (!f || !out) return fail(PT_E_INVALID, "pt_film_get_merge_info: NULL argument");
+  std::memset(out, 0, sizeof(*out));
+  if (!f->t_mg.timed) return PT_OK;
+  HIPCHK(hipSetDevice(f->ctx->device));
+  float ms = 0.f;
+  HIPCHK(f->t_mg.ms(&ms));
+  unsigned long long n[4] = {0, 0, 0, 0};
+  HIPCHK(hipMemcpy(n, f->mg_counts.p, sizeof(n), hipMemcpyDeviceToHost));
+  out->merged = (int64_t)n[0];
+  out->taken = (int64_t)n[1];
+  out->empty = (int64_t)n[2];
+  out->refused = (int64_t)n[3];
+  out->merge_ms = ms;
+  return PT_OK;
+}
+
+int pt_debug_film_records(pt_film* f, void** rec_dev) {
+  if (!f || !rec_dev) return fail(PT_E_INVALID, "pt_debug_film_records: NULL argument");
+  *rec_dev = f->rec.p;
+  return PT_OK;
+}
+
 int pt_to_color_device(pt_ctx* c, const float* hdr_dev, int32_t width, int32_t height, int32_t x0, int32_t y0,
                        int32_t x1, int32_t y1, uint32_t* rgba_dev, void* stream) {
   if (!c || !hdr_dev || !rgba_dev || width < 0 || height < 0) return fail(PT_E_INVALID, "pt_to_color_device: bad args");

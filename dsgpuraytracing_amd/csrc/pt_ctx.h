@@ -198,6 +198,11 @@ struct pt_film {
   DevBuf<float4> feat2;
   DevBuf<unsigned long long> rp_counts;
   TimedSpan t_rp;
+  // pt_film_merge*: the device side of host records, the four class counts of
+  // the last merge and the time of its kernel (allocated at first use)
+  DevBuf<uint4> mg_stage;
+  DevBuf<unsigned long long> mg_counts;
+  TimedSpan t_mg;
   uint64_t next = 0;  // next sample index (<= 2^32)
   int64_t passes = 0;
   TimedSpan t_acc, t_res;  // the last accumulate / resolve kernel

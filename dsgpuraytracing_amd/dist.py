@@ -23,6 +23,10 @@ collective:
     queued behind its resolve on the current stream; the renders run on the
     library's render-slot streams, so they overlap frame k+1's render (a
     side-stream variant behind events is kept for A/Bs).
+  * progressive films (pathtracer.Film) split the same two ways -- by tiles
+    (film_passes_tile_split) or by sample ranges (film_passes_sample_split) --
+    and FilmExchange joins them on one rank: one gather of the exported
+    records, then pt_film_merge_device in rank order.
 """
 from __future__ import annotations
 
@@ -283,6 +287,126 @@ def render_sharded(render_packed: Callable[[List[Tile], object], None], frame, t
     ex.exchange(frame)
     guard.check()
     return frame
+
+
+class FilmExchange:
+    """Joins the films of a split progressive render on one rank.
+
+    Every rank holds a film of the same W x H frame (pathtracer.Film); the
+    films are joined by merging their exported records (include/ptgpu.h:
+    pt_film_export* / pt_film_merge*).  Like render_sharded this takes
+    callables, so the same schedule runs on numpy records over gloo (tests)
+    and on device films over RCCL:
+      export(buf)  writes this rank's records into `buf`, a (2, H, W, 4) int32
+                   tensor on `device` (the records' 32-bit words; on the device
+                   Film.export_device(buf.data_ptr(), current stream));
+      merge(buf)   merges the records in such a tensor into this rank's film
+                   (Film.merge_device(buf.data_ptr(), current stream)).
+    On the device both are queued on torch's current stream, as TileExchange
+    asks of the render: the collective is ordered after that stream's work.
+    The merge is not bitwise commutative, so the order is fixed: the root
+    merges the other ranks' records in rank order."""
+
+    def __init__(self, width: int, height: int, rank: int, world: int, device, group=None):
+        import torch
+
+        if world < 1 or not 0 <= rank < world:
+            raise ValueError(f"bad rank/world {rank}/{world}")
+        self.width, self.height, self.rank, self.world, self.group = width, height, rank, world, group
+        self.send = torch.zeros((2, height, width, 4), dtype=torch.int32, device=device)
+        self.recv = None  # (world, 2, H, W, 4) on the root, allocated by its first gather
+
+    def gather(self, export, dst: int = 0):
+        """Every rank's exported records into `recv[rank]` on `dst` (one
+        collective; with an initialised process group also at world size 1, so
+        the RCCL path is the one a 1-GPU test exercises).  Returns `recv` on
+        `dst`, None elsewhere."""
+        import torch
+        import torch.distributed as dist
+
+        coll = dist.is_available() and dist.is_initialized()
+        if self.world > 1 and not coll:
+            raise RuntimeError(f"FilmExchange: world size {self.world} without an initialised process group")
+        root = self.rank == dst
+        if root and self.recv is None:
+            self.recv = torch.zeros((self.world,) + tuple(self.send.shape), dtype=torch.int32, device=self.send.device)
+        export(self.send)
+        if coll and self.send.is_cuda and dist.get_backend(self.group) == "gloo":
+            # gloo gathers host tensors only (tests / one-GPU rehearsals)
+            src = self.send.cpu()
+            gl = [torch.empty_like(src) for _ in range(self.world)] if root else None
+            dist.gather(src, gather_list=gl, dst=dst, group=self.group)
+            if root:
+                self.recv.copy_(torch.stack(gl))
+        elif coll:
+            gl = list(self.recv.unbind(0)) if root else None
+            dist.gather(self.send, gather_list=gl, dst=dst, group=self.group)
+        else:
+            self.recv[0].copy_(self.send)
+        return self.recv if root else None
+
+    def merge_to_root(self, export, merge, dst: int = 0):
+        """One gather of every rank's records onto `dst`, which then merges
+        the other ranks' in rank order: afterwards `dst` holds the joined
+        film; the other ranks' films are unchanged.  Nothing to do for one
+        rank."""
+        if self.world == 1:
+            return
+        recv = self.gather(export, dst)
+        if self.rank == dst:
+            for r in range(self.world):
+                if r != dst:
+                    merge(recv[r])
+
+
+def _check_sample_range(first: int, count: int, what: str):
+    if first < 0 or count < 0 or first + count > 2 ** 32:
+        raise ValueError(f"{what}: samples {first} .. {first + count} pass 2^32 (a film's sample index is 32 bits)")
+
+
+def film_passes_tile_split(film, tiles: Sequence[Tile], passes: int, rank: int, world: int, spp: int = 0,
+                           deal: str = "mod", tile_size: int = TILE, stream: int = 0) -> List[Tile]:
+    """A rank's part of a tile split: `passes` passes over its shard_tiles
+    share of `tiles` on `film` (a pathtracer.Film whose context holds the
+    params; every rank starts at the same next sample index).  After
+    FilmExchange.merge_to_root the root's film equals the film that rendered
+    every tile, bit for bit: each pixel is one rank's, so every pixel is taken
+    or empty.  spp (the params' samples per pass), when given, refuses up
+    front a range that would pass 2^32; otherwise the film refuses the pass
+    that would.  Returns the rank's tiles."""
+    mine = shard_tiles(tiles, rank, world, deal, tile_size)
+    if passes < 0 or spp < 0:
+        raise ValueError(f"film_passes_tile_split: bad passes/spp {passes}/{spp}")
+    if spp:
+        _check_sample_range(int(film.info()["next_sample"]), passes * spp, "film_passes_tile_split")
+    for _ in range(passes):
+        film.add_pass(mine, stream=stream)
+    return mine
+
+
+def film_passes_sample_split(film, tiles: Sequence[Tile], passes: int, spp: int, rank: int, world: int,
+                             stream: int = 0) -> Tuple[int, int]:
+    """A rank's part of a sample split: rank r renders all of `tiles` for
+    `passes` passes of `spp` samples (the context's params' spp) over the
+    sample indices [r * passes * spp, (r + 1) * passes * spp), so the ranks
+    together draw the sample set of one film of world * passes passes.
+    After FilmExchange.merge_to_root the root holds their merge.  Refused on
+    every rank when the whole split's range would pass 2^32.  Returns the
+    rank's (first, end) sample indices."""
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"bad rank/world {rank}/{world}")
+    if passes < 0 or spp < 1:
+        raise ValueError(f"film_passes_sample_split: bad passes/spp {passes}/{spp}")
+    _check_sample_range(0, world * passes * spp, "film_passes_sample_split")
+    first = rank * passes * spp
+    film.set_next_sample(first)
+    for _ in range(passes):
+        film.add_pass(tiles, stream=stream)
+    end = int(film.info()["next_sample"])
+    if end != first + passes * spp:
+        raise RuntimeError(f"film_passes_sample_split: the passes drew samples {first} .. {end}, not "
+                           f"{passes} x {spp}: the context's params hold another spp")
+    return first, end
 
 
 # Environment knobs of libptgpu.so that change pixel VALUES (not only speed):

@@ -104,6 +104,11 @@ class pt_film_info(ctypes.Structure):
                 ("accumulate_ms", c_double), ("resolve_ms", c_double)]
 
 
+class pt_film_merge_info(ctypes.Structure):
+    _fields_ = [("merged", c_int64), ("taken", c_int64), ("empty", c_int64), ("refused", c_int64),
+                ("merge_ms", c_double)]
+
+
 class pt_denoise_params(ctypes.Structure):
     _fields_ = [("iterations", c_int32), ("normal_squarings", c_int32), ("sigma_l", c_float), ("sigma_p", c_float)]
 
@@ -165,6 +170,12 @@ _SIGS = {
     "pt_film_tile_error": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p]),
     "pt_film_get_info": (c_int32, [c_void_p, POINTER(pt_film_info)]),
     "pt_film_set_next_sample": (c_int32, [c_void_p, c_uint32]),
+    "pt_film_export_device": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "pt_film_export": (c_int32, [c_void_p, c_void_p]),
+    "pt_film_merge_device": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "pt_film_merge": (c_int32, [c_void_p, c_void_p]),
+    "pt_film_get_merge_info": (c_int32, [c_void_p, POINTER(pt_film_merge_info)]),
+    "pt_debug_film_records": (c_int32, [c_void_p, POINTER(c_void_p)]),
     "pt_render_features_device": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p, c_void_p]),
     "pt_render_features": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p]),
     "pt_denoise_params_default": (c_int32, [POINTER(pt_denoise_params)]),

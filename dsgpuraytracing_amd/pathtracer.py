@@ -402,6 +402,66 @@ class Film:
         check(self._lib.pt_film_get_info(self.handle, ctypes.byref(i)))
         return {k: getattr(i, k) for k, _ in native.pt_film_info._fields_}
 
+    def export(self) -> np.ndarray:
+        """The film's records, (2, H, W, 4) uint32: plane 0 {sum.r, sum.g,
+        sum.b, n}, plane 1 {mu, M2, k, pad}, floats as their bits
+        (pt_film_export; waits)."""
+        out = np.empty((2, self.height, self.width, 4), np.uint32)
+        check(self._lib.pt_film_export(self.handle, out.ctypes.data))
+        return out
+
+    def export_device(self, ptr: int, stream: int = 0):
+        """pt_film_export_device: the records into the device buffer at `ptr`
+        (2 * H * W * 16 bytes); queued on `stream`."""
+        check(self._lib.pt_film_export_device(self.handle, ctypes.c_void_p(ptr or None),
+                                              ctypes.c_void_p(stream or None)))
+
+    def merge(self, records: np.ndarray):
+        """film <- film (+) records (pt_film_merge; waits): `records` as
+        export() returns them, of a film of this frame size.  Not bitwise
+        commutative: merge in a fixed order for reproducible bits."""
+        rec = np.ascontiguousarray(records, dtype=np.uint32)
+        if rec.shape != (2, self.height, self.width, 4):
+            raise ValueError(f"Film.merge: need records of shape {(2, self.height, self.width, 4)}, got {rec.shape}")
+        check(self._lib.pt_film_merge(self.handle, rec.ctypes.data))
+
+    def merge_device(self, ptr: int, stream: int = 0):
+        """pt_film_merge_device: the records in the device buffer at `ptr`
+        (not the film's own) merged into the film; queued on `stream`."""
+        check(self._lib.pt_film_merge_device(self.handle, ctypes.c_void_p(ptr or None),
+                                             ctypes.c_void_p(stream or None)))
+
+    def merge_info(self) -> dict:
+        """merged / taken / empty / refused pixel counts and the kernel's
+        device time of the last merge (pt_film_get_merge_info; waits)."""
+        i = native.pt_film_merge_info()
+        check(self._lib.pt_film_get_merge_info(self.handle, ctypes.byref(i)))
+        return {k: getattr(i, k) for k, _ in native.pt_film_merge_info._fields_}
+
+    def save(self, path):
+        """A checkpoint: the records, the frame size and the next sample index
+        in one .npz (np.savez: a path without the suffix gets it)."""
+        np.savez(path, records=self.export(), width=np.int64(self.width), height=np.int64(self.height),
+                 next_sample=np.uint64(self.info()["next_sample"]))
+
+    @classmethod
+    def load(cls, dev: Device, path) -> "Film":
+        """A new film of `dev` from a checkpoint of save(): the merge into the
+        clear film takes every record bit for bit, then the next sample index
+        is set, so further passes continue the saved render."""
+        with np.load(path) as z:
+            rec, w, h, nxt = z["records"], int(z["width"]), int(z["height"]), int(z["next_sample"])
+        if not 0 <= nxt < 2 ** 32:  # (pt_film_set_next_sample takes a uint32: a film at 2^32 has no sample left)
+            raise ValueError(f"Film.load: next_sample {nxt} of {path!r} is outside 0 .. 2^32 - 1")
+        film = cls(dev, w, h)
+        try:
+            film.merge(rec)
+            film.set_next_sample(nxt)
+        except Exception:
+            film.close()
+            raise
+        return film
+
 
 def to_color_device(dev: Device, hdr_ptr: int, w: int, h: int, rgba_ptr: int, rect=None, stream: int = 0):
     """pt_to_color_device: to_color of the device buffer at hdr_ptr ((h, w, 3)

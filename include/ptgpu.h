@@ -45,6 +45,9 @@
  *   pt_film_*                   no counterpart: a device-resident progressive film (accumulated
  *                               passes, per-pixel error, GPU resolve to HDR / RGBA8 / error) for
  *                               the display loop that redraws frameBuffer (application.cpp:142-160)
+ *   pt_film_export* / pt_film_merge*   no counterpart: a film's records copied out, and another
+ *                               film's records combined into it (two Welford states merged per
+ *                               pixel): films of a multi-GPU tile or sample split, checkpoints
  *   pt_render_features*         no counterpart: the camera ray's Intersection (trace_ray,
  *                               pathtracer.cpp:435-456) kept per pixel: normal, hit point, depth, BSDF
  *   pt_denoise_* / pt_film_denoise*   no counterpart: an edge-avoiding filter of the film's mean,
@@ -498,6 +501,71 @@ int pt_film_get_info(pt_film* film, pt_film_info* out);
 /* Sets the sample index the next pass starts at (a film that continues an
  * earlier render, or one rank's share of a sample split).  Host state only. */
 int pt_film_set_next_sample(pt_film* film, uint32_t next_sample);
+
+/* ---- The film's records out and in: export and merge (no reference
+ * counterpart).  A record buffer of a W x H film is 2*W*H*16 bytes in the
+ * film's own layout, pixel p = x + y*W, y = 0 the bottom row:
+ *   rec[p]       = {sum.r, sum.g, sum.b, n}   f32 f32 f32 u32
+ *   rec[W*H + p] = {mu, M2, k, pad}           f32 f32 u32 u32
+ * pt_film_export* copies the film's records out.  pt_film_merge* combines
+ * incoming records into the film, film <- film (+) rec: per pixel the pairwise
+ * combine of two Welford states (Chan, Golub, LeVeque 1979).  With it the
+ * films of a multi-GPU split are joined (each rank's film over its own tiles,
+ * or one film per sample range set with pt_film_set_next_sample), and a film
+ * is checkpointed: restore = pt_film_create + pt_film_merge of the saved
+ * records + pt_film_set_next_sample; the merge into a clear film takes every
+ * pixel bit for bit.
+ *
+ * Like the film's, the arithmetic is a definition: every operator one
+ * separately rounded IEEE f32 operation in the order written, nothing fused,
+ * `/` correctly rounded.  For pixel p, a = the film's two records, b = the
+ * incoming ones; each pixel falls into exactly one class:
+ *   empty    n_b == 0:                      a is unchanged
+ *   taken    n_a == 0, n_b > 0:             both records become b's bit for bit, pad included
+ *   refused  n_a + n_b does not fit in 32 bits:   a is unchanged
+ *   merged   otherwise:
+ *     sum_c = sum_a_c + sum_b_c                           c = r, g, b
+ *     n     = n_a + n_b
+ *     W     = (float)n
+ *     d     = mu_b - mu_a
+ *     mu    = mu_a + d * ((float)n_b / W)
+ *     M2    = (M2_a + M2_b) + (d * d) * (((float)n_a * (float)n_b) / W)
+ *     k     = k_a + k_b
+ *     pad   = pad_a
+ * The merge is NOT bitwise commutative or associative (a (+) b and b (+) a
+ * round differently): a caller who needs reproducible bits merges in a fixed
+ * order, as dist.FilmExchange merges ranks 1 .. N-1 into rank 0 in rank order.
+ * Where the two films cover disjoint pixels every pixel is taken or empty and
+ * the order does not matter.
+ *
+ * passes, next_sample, the feature records and their presence are not
+ * touched: a caller who continues a render calls pt_film_set_next_sample.
+ * The incoming records must be a film's (finite, k <= n): the kernel checks
+ * nothing but the overflow of n.  PT_E_INVALID, film unchanged: a NULL film or
+ * buffer, or a device buffer that overlaps the film's own records.  Stream
+ * semantics and cross-stream ordering as the other film calls: the _device
+ * calls return when queued and read / write the caller's buffer in `stream`
+ * order; the host calls wait (pt_film_merge stages through a buffer the film
+ * owns). */
+typedef struct pt_film_merge_info {
+  int64_t merged;   /* pixels of the last merge per class; the four sum to W*H */
+  int64_t taken;
+  int64_t empty;
+  int64_t refused;
+  double merge_ms;  /* device time of the last merge kernel (hipEvent) */
+} pt_film_merge_info;
+int pt_film_export_device(pt_film* film, void* rec_out_dev, void* stream);
+int pt_film_export(pt_film* film, void* rec_out_host);
+int pt_film_merge_device(pt_film* film, const void* rec_dev, void* stream);
+int pt_film_merge(pt_film* film, const void* rec_host);
+/* Of the film's last merge (all zero before the first); waits for it. */
+int pt_film_get_merge_info(pt_film* film, pt_film_merge_info* out);
+/* Diagnostics: the device address of the film's own records at the moment
+ * (a pt_film_reproject swaps them for another allocation), so that a test can
+ * hand pt_film_merge_device / pt_film_export_device a buffer that overlaps
+ * them.  Not for reading or writing the records: export and merge do that in
+ * stream order. */
+int pt_debug_film_records(pt_film* film, void** rec_dev);
 
 /* ---- First-hit feature buffers (no reference counterpart: the reference's
  * Intersection of the camera ray, trace_ray pathtracer.cpp:435-456, never
