@@ -814,6 +814,83 @@ int64_t pt_env_search_check(const float* rgb, int32_t width, int32_t height, int
   return bad;
 }
 
+// The float tables build_env_tables makes for a map, as the upload sends them
+// to the device (host only): what a test-side reference searches and divides by.
+int pt_env_tables(const float* rgb, int32_t width, int32_t height, float* p_theta, float* p_phi, float* pdf) {
+  if (!rgb || width <= 0 || height <= 0) return fail(PT_E_INVALID, "pt_env_tables: bad arguments");
+  EnvTables t;
+  build_env_tables(rgb, width, height, t);
+  if (p_theta) std::copy(t.p_theta.begin(), t.p_theta.end(), p_theta);
+  if (p_phi) std::copy(t.p_phi.begin(), t.p_phi.end(), p_phi);
+  if (pdf) std::copy(t.p_theta_phi.begin(), t.p_theta_phi.end(), pdf);
+  return PT_OK;
+}
+
+// The environment light's device functions on the uploaded tables, one lane
+// per query (env_probe_kernel).  Every query is checked here first: the kernel
+// forms its table indices from them and is never launched on one it could not
+// answer inside the tables.
+int pt_debug_env_probe(pt_ctx* c, int64_t n, const float* u1, const float* u2, int32_t* row, int32_t* col,
+                       float* row_pair, float* col_pair, float* wi, float* pdf, float* tu, float* tv, float* radiance,
+                       int64_t m, const float* dirs, float* dir_radiance) {
+  // (the queries first: they are refused without a device, too)
+  const int64_t kMax = 1 << 24;
+  if (n < 0 || m < 0 || n > kMax || m > kMax) return fail(PT_E_INVALID, "pt_debug_env_probe: bad query count");
+  if (n > 0 && (!u1 || !u2 || !row || !col || !row_pair || !col_pair || !wi || !pdf || !tu || !tv || !radiance))
+    return fail(PT_E_INVALID, "pt_debug_env_probe: NULL sample argument");
+  if (m > 0 && (!dirs || !dir_radiance)) return fail(PT_E_INVALID, "pt_debug_env_probe: NULL direction argument");
+  for (int64_t i = 0; i < n; ++i)
+    if (!(u1[i] >= 0.0f && u1[i] < 1.0f && u2[i] >= 0.0f && u2[i] < 1.0f))
+      return fail(PT_E_INVALID, "pt_debug_env_probe: sample query " + std::to_string(i) + " outside [0, 1)");
+  for (int64_t i = 0; i < m; ++i) {
+    const double x = dirs[3 * i], y = dirs[3 * i + 1], z = dirs[3 * i + 2];
+    const double len = std::sqrt(x * x + y * y + z * z);
+    if (!std::isfinite(len) || std::fabs(len - 1.0) > 1e-3)
+      return fail(PT_E_INVALID, "pt_debug_env_probe: direction " + std::to_string(i) + " is not a unit vector");
+  }
+  if (!c) return fail(PT_E_INVALID, "NULL context");
+  if (!c->have_scene) return fail(PT_E_NOSCENE, "pt_debug_env_probe before pt_upload_scene");
+  const DeviceScene& sc = c->scene;
+  if (sc.env_w <= 0 || sc.env_h <= 0) return fail(PT_E_INVALID, "pt_debug_env_probe: the scene has no environment light");
+  if (n == 0 && m == 0) return PT_OK;
+  HIPCHK(hipSetDevice(c->device));
+  const size_t n_in = (size_t)(2 * n + 3 * m), n_out = (size_t)(13 * n + 3 * m);
+  std::vector<float> in(n_in);
+  std::copy(u1, u1 + n, in.begin());
+  std::copy(u2, u2 + n, in.begin() + n);
+  std::copy(dirs, dirs + 3 * m, in.begin() + 2 * n);
+  HIPCHK(c->q_f.reserve(n_in + n_out));
+  HIPCHK(c->q_i.reserve((size_t)(2 * n)));
+  HIPCHK(hipMemcpyAsync(c->q_f.p, in.data(), n_in * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  EnvProbe a{};
+  a.env_w = sc.env_w, a.env_h = sc.env_h;
+  a.env_tex = sc.env_tex.p;
+  a.env_ptheta = sc.env_ptheta.p, a.env_pphi = sc.env_pphi.p, a.env_pdf = sc.env_pdf.p;
+  a.env_rtheta = sc.env_rtheta.p, a.env_rphi = sc.env_rphi.p;
+  a.n = (int)n, a.u = c->q_f.p, a.idx = c->q_i.p, a.out = c->q_f.p + n_in;
+  a.m = (int)m, a.d = c->q_f.p + 2 * n, a.rad = c->q_f.p + n_in + 13 * n;
+  HIPCHK(ptk_launch_env_probe(&a, c->stream));
+  std::vector<float> out(n_out);
+  std::vector<int32_t> idx((size_t)(2 * n));
+  HIPCHK(hipMemcpyAsync(out.data(), a.out, n_out * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (n > 0) HIPCHK(hipMemcpyAsync(idx.data(), a.idx, idx.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (n > 0) {
+    const float* o = out.data();
+    std::copy(idx.begin(), idx.begin() + n, row);
+    std::copy(idx.begin() + n, idx.end(), col);
+    std::copy(o, o + 2 * n, row_pair);
+    std::copy(o + 2 * n, o + 4 * n, col_pair);
+    std::copy(o + 4 * n, o + 7 * n, wi);
+    std::copy(o + 7 * n, o + 8 * n, pdf);
+    std::copy(o + 8 * n, o + 9 * n, tu);
+    std::copy(o + 9 * n, o + 10 * n, tv);
+    std::copy(o + 10 * n, o + 13 * n, radiance);
+  }
+  if (m > 0) std::copy(out.begin() + 13 * n, out.end(), dir_radiance);
+  return PT_OK;
+}
+
 int pt_get_stats(pt_ctx* c, pt_stats* out) {
   if (!c || !out) return fail(PT_E_INVALID, "pt_get_stats: NULL argument");
   int rc = settle_times(c);

@@ -142,7 +142,7 @@ struct pt_ctx {
   TileSeam seam;
   DevBuf<int> q_spill;  // ray-query stack spill
   DevBuf<unsigned long long> stats;
-  DevBuf<float> q_f;  // ray-query scratch
+  DevBuf<float> q_f;  // scratch of the query entry points (pt_intersect, pt_debug_env_probe): inputs and outputs
   DevBuf<int32_t> q_i;
   bool have_scene = false, have_cam = false, have_params = false;
   pt_camera cam{};

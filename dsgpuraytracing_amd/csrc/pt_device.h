@@ -184,6 +184,29 @@ extern "C" hipError_t ptk_launch_intersect(const DNode* nodes, const DPrim* prim
                                            int32_t* anyhit, int* spill, const int* prim_map, hipStream_t s);
 extern "C" hipError_t ptk_render_occupancy(int* waves_per_cu, bool stats, bool env, bool gtab);
 
+// Environment-light probe (env_probe_kernel; ptgpu.h pt_debug_env_probe): the
+// env_* fields as KParams names them -- env_sample, env_uv and env_dir are
+// templates over the parameter struct -- and the queries.  One lane per query.
+struct EnvProbe {
+  int env_w, env_h;
+  const float4* env_tex;
+  const float* env_ptheta;
+  const float* env_pphi;
+  const float* env_pdf;
+  const struct EnvRec* env_rtheta;
+  const struct EnvRec* env_rphi;
+  int n;           // sample queries
+  const float* u;  // u1[n], then u2[n], each in [0, 1)
+  int32_t* idx;    // row[n], col[n]
+  // prev / cur of the row search (2n, interleaved), of the column search (2n),
+  // wi (3n), pdf (n), tu (n), tv (n), env_uv(tu, tv) (3n): 13n floats
+  float* out;
+  int m;           // direction queries
+  const float* d;  // 3m, finite and of unit length
+  float* rad;      // env_dir(d): 3m
+};
+extern "C" hipError_t ptk_launch_env_probe(const EnvProbe* a, hipStream_t s);
+
 // First-hit feature pass (features_kernel; ptgpu.h pt_render_features_device):
 // the camera as KParams holds it, the render tree, and the output records.
 struct FeatArgs {

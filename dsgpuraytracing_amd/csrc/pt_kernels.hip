@@ -673,6 +673,13 @@ __device__ __forceinline__ void env_sample(const KP& P, float r1, float r2, floa
   float st, ct, sp, cp;
   __sincosf(theta, &st, &ct);
   __sincosf(phi, &sp, &cp);
+  // A draw at the top of the last row (u1 within a float step of 1 where that
+  // row holds mass) rounds y / h to 1: theta is float pi, whose fast sine is 0
+  // -- a pdf of +inf (the reference's own float theta there has a negative
+  // sine, and pdf).  The sine of a latitude is positive inside (0, pi]: at
+  // least the one of the last float step before the pole.  theta == 0 (u1 == 0)
+  // keeps its sine of 0, as the reference has it.
+  st = fmaxf(st, fminf(theta, 0x1p-24f));
   pdf = P.env_pdf[(size_t)t * w + q] / (st * ((2.0f * kPi / (float)w) * (kPi / (float)h)));
   wi = f3(-st * sp, ct, st * cp);
 }
@@ -1902,6 +1909,47 @@ extern "C" hipError_t ptk_render_occupancy_env(int* waves_per_cu, bool gtab) {
                             &blocks, ptk::render_kernel<false, false, false, true, false>, PT_BLOCK, 0);
   *waves_per_cu = blocks;
   return e;
+}
+
+// pt_debug_env_probe: the render kernel's own environment-light functions, one
+// lane per query.  Lane i < n replays the two searches of env_sample with the
+// arguments env_sample gives them (row, column and their interpolation pairs),
+// then calls env_sample itself and env_uv at the coordinates it returned;
+// lane i < m calls env_dir.  The host has checked every query (u in [0, 1),
+// unit directions), so every index the functions form lies inside the tables.
+namespace ptk {
+__global__ __launch_bounds__(PT_BLOCK) void env_probe_kernel(EnvProbe A) {
+  const int i = (int)(blockIdx.x * PT_BLOCK + threadIdx.x);
+  if (i < A.n) {
+    const int n = A.n, w = A.env_w, h = A.env_h;
+    const float u1 = A.u[i], u2 = A.u[n + i];
+    float prev, cur;
+    const float r1 = u1 * A.env_ptheta[h - 1];
+    const int t = record_lower_bound(A.env_ptheta, r1, u1, A.env_rtheta, PT_ENV_GUIDE, prev, cur);
+    A.idx[i] = t;
+    A.out[2 * i] = prev, A.out[2 * i + 1] = cur;
+    const float* row = A.env_pphi + (size_t)t * w;
+    const float r2 = u2 * row[w - 1];
+    const int q = record_lower_bound(row, r2, u2, A.env_rphi + (size_t)t * PT_ENV_GUIDE, PT_ENV_GUIDE, prev, cur);
+    A.idx[n + i] = q;
+    A.out[2 * n + 2 * i] = prev, A.out[2 * n + 2 * i + 1] = cur;
+    float3 wi;
+    float pdf, tu, tv;
+    env_sample(A, u1, u2, wi, pdf, tu, tv);
+    store3(A.out + 4 * n + 3 * i, wi);
+    A.out[7 * n + i] = pdf;
+    A.out[8 * n + i] = tu;
+    A.out[9 * n + i] = tv;
+    store3(A.out + 10 * n + 3 * i, env_uv(A, tu, tv));
+  }
+  if (i < A.m) store3(A.rad + 3 * i, env_dir(A, ld3(A.d + 3 * i)));
+}
+}  // namespace ptk
+extern "C" hipError_t ptk_launch_env_probe(const EnvProbe* a, hipStream_t s) {
+  const int grid = ((a->n > a->m ? a->n : a->m) + PT_BLOCK - 1) / PT_BLOCK;
+  if (grid <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ptk::env_probe_kernel, dim3(grid), dim3(PT_BLOCK), 0, s, *a);
+  return hipGetLastError();
 }
 #else
 extern "C" hipError_t ptk_launch_render_env(const KParams* P, int grid, bool stats, bool ref_counts, bool gtab,

@@ -190,6 +190,8 @@ _SIGS = {
     "pt_film_reproject": (c_int32, [c_void_p, POINTER(pt_reproject_params), c_void_p]),
     "pt_film_get_reproject_info": (c_int32, [c_void_p, POINTER(pt_reproject_info)]),
     "pt_env_search_check": (c_int64, [c_void_p, c_int32, c_int32, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
+    "pt_env_tables": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "pt_debug_env_probe": (c_int32, [c_void_p, c_int64] + [c_void_p] * 11 + [c_int64, c_void_p, c_void_p]),
     # include/ptgpu_scene.h (bound with full types in scene_loader.py)
     "pt_host_scene_load": (c_int32, [c_char_p, c_int32, c_int32, c_char_p, POINTER(c_void_p)]),
     "pt_host_scene_view": (c_int32, [c_void_p, c_void_p, c_void_p]),

@@ -208,6 +208,30 @@ class Device:
         d["root_hi"] = np.array(list(info.root_hi), np.float32)
         return {"info": d, "nodes4": nodes4, "nodes2": nodes2, "prims": prims, "norms": norms, "prim_map": prim_map}
 
+    def env_probe(self, u1=(), u2=(), dirs=()) -> dict:
+        """pt_debug_env_probe: the render kernel's environment-light functions
+        on the uploaded tables.  For the pairs (u1, u2) in [0, 1): `row`, `col`
+        (int32), `row_pair`, `col_pair` ((n, 2) float32: prev, cur), `wi`
+        (n, 3), `pdf`, `tu`, `tv` (n,) and `radiance` (n, 3); for the unit
+        directions `dirs` (m, 3): `dir_radiance` (m, 3).  Invalid queries are
+        refused (PtError) before anything runs on the device."""
+        u1 = np.ascontiguousarray(u1, np.float32).reshape(-1)
+        u2 = np.ascontiguousarray(u2, np.float32).reshape(-1)
+        if len(u1) != len(u2):
+            raise ValueError("env_probe: u1 and u2 differ in length")
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        n, m = len(u1), len(d)
+        o = {"row": np.zeros(n, np.int32), "col": np.zeros(n, np.int32), "row_pair": np.zeros((n, 2), np.float32),
+             "col_pair": np.zeros((n, 2), np.float32), "wi": np.zeros((n, 3), np.float32), "pdf": np.zeros(n, np.float32),
+             "tu": np.zeros(n, np.float32), "tv": np.zeros(n, np.float32), "radiance": np.zeros((n, 3), np.float32),
+             "dir_radiance": np.zeros((m, 3), np.float32)}
+        ptr = lambda a, k: a.ctypes.data if k else None
+        check(self._lib.pt_debug_env_probe(
+            self.handle, n, ptr(u1, n), ptr(u2, n), *[ptr(o[k], n) for k in ("row", "col", "row_pair", "col_pair", "wi",
+                                                                            "pdf", "tu", "tv", "radiance")],
+            m, ptr(d, m), ptr(o["dir_radiance"], m)))
+        return o
+
     def render_features(self, tiles=None) -> dict:
         """First-hit feature buffers of `tiles` (the whole frame by default;
         pt_render_features, waits): `normal` (H, W, 3) float32, `position`
@@ -585,6 +609,17 @@ def to_color(hdr: np.ndarray) -> np.ndarray:
     frame = np.zeros((h, w), np.uint32)
     native.check(native.lib().pt_to_color(hdr.ctypes.data, w, h, 0, 0, w, h, frame.ctypes.data))
     return frame.view(np.uint8).reshape(h, w, 4)
+
+
+def env_tables(rgb: np.ndarray):
+    """pt_env_tables: EnvironmentLight's float32 tables of an (H, W, 3) map as
+    an upload builds them (host only): p_theta (H,), p_phi (H, W), pdf (H, W)."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    h, w = rgb.shape[:2]
+    p_theta, p_phi, pdf = np.zeros(h, np.float32), np.zeros((h, w), np.float32), np.zeros((h, w), np.float32)
+    native.check(native.lib().pt_env_tables(rgb.ctypes.data, w, h, p_theta.ctypes.data, p_phi.ctypes.data,
+                                            pdf.ctypes.data))
+    return p_theta, p_phi, pdf
 
 
 class PathTracer:

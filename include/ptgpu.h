@@ -790,6 +790,29 @@ int64_t pt_to_color_check(uint32_t lo_bits, uint32_t hi_bits);
  * receives how many searches took the window-halving path. */
 int64_t pt_env_search_check(const float* rgb, int32_t width, int32_t height, int64_t n, const float* u1,
                             const float* u2, int64_t* long_windows);
+/* Diagnostics (host only, no context): EnvironmentLight's float tables for the
+ * width x height float RGB map exactly as an upload builds them and sends them to
+ * the device -- p_theta[height] (pTheta, running sums over rows), p_phi[height *
+ * width] (pPhiGivenTheta, running sums within each row) and pdf[height * width]
+ * (pThetaPhi).  Any output pointer may be NULL and is skipped.  PT_E_INVALID for a
+ * NULL map or a non-positive size. */
+int pt_env_tables(const float* rgb, int32_t width, int32_t height, float* p_theta, float* p_phi, float* pdf);
+/* Diagnostics (no reference counterpart): the render kernel's own environment-light
+ * device functions on the uploaded scene's tables, one lane per query; waits.
+ * For each of n pairs (u1[i], u2[i]) in [0, 1): the row and column that the two
+ * inverse-CDF searches of the sampler return (pt_device.h record_lower_bound, called
+ * with the sampler's arguments) and their interpolation pairs row_pair[2i], [2i+1] =
+ * (prev, cur), col_pair likewise; then the sampler itself: wi[3i..], pdf[i] and the
+ * texel coordinates (tu[i], tv[i]) it drew at, and radiance[3i..], the bilinear
+ * lookup at those coordinates.  For each of m unit directions dirs[3j..]:
+ * dir_radiance[3j..], the lookup by direction (EnvironmentLight::sample_dir).
+ * Nothing is launched unless every query is valid: PT_E_INVALID for a negative or
+ * too large (> 2^24) count, a NULL pointer with a positive count, a u outside
+ * [0, 1), a non-finite direction or one whose length is not within 1e-3 of 1, and
+ * for a scene without an environment light; PT_E_NOSCENE before an upload. */
+int pt_debug_env_probe(pt_ctx* ctx, int64_t n, const float* u1, const float* u2, int32_t* row, int32_t* col,
+                       float* row_pair, float* col_pair, float* wi, float* pdf, float* tu, float* tv, float* radiance,
+                       int64_t m, const float* dirs, float* dir_radiance);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,14 @@ environment_light.cpp:69-115) replayed on the host against std::lower_bound
 (pt_env_search_check).  The window-halving path runs where a guide bucket's
 window spans more than four entries: maps wider than the 1024-bucket guide
 table, and nearly flat stretches of a peaky map -- ADVICE r4 found the halved
-window returning the whole window's last value as `cur` there."""
+window returning the whole window's last value as `cur` there.
+
+This replays the HOST body of record_lower_bound.  Its device body (two 16-byte
+vector loads and bit-casts of the record, under __HIP_DEVICE_COMPILE__) has a
+check of its own: pt_debug_env_probe runs it on a GPU and
+tests/test_gpu_env_maps.py::test_probe_search_is_bit_exact compares row, column
+and interpolation pair with np.searchsorted over the same tables, on the hard
+maps of tests/env_maps.py."""
 import ctypes
 
 import numpy as np
