@@ -167,6 +167,20 @@ struct pt_ctx {
   // the last waits for it
   DevList<uint32_t> rp_keep;
   StreamOrder rp_order;
+  // ray queries on the device (pt_trace_rays*, pt_camera_rays_device): the
+  // spill area of the bounded grid and the {rays, hits, invalid} counter, both
+  // reused from call to call -- a trace that comes on another stream than the
+  // last waits for it --, the last trace's kernel time, the device side of the
+  // host entry point's rays and results, the camera rays' tile list
+  DevBuf<int> tr_spill;
+  DevBuf<unsigned long long> tr_counts;
+  TimedSpan t_trace;
+  bool tr_counted = false;  // the last trace launched a kernel: tr_counts and t_trace are its
+  StreamOrder tr_order;
+  DevBuf<float4> tr_rays, tr_out;
+  int bpc_trace[2] = {0, 0};  // resident one-wave workgroups per CU: closest, occluded (asked for at first use)
+  DevList<int4> cr_tiles;
+  StreamOrder cr_order;
   // Every member frees itself, in reverse order of declaration; only what
   // needs ordering is done here: no kernel may still be running when the
   // first member goes.

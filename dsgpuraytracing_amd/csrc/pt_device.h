@@ -224,3 +224,37 @@ struct FeatArgs {
 };
 // One wave per 64 pixels (an 8x8 block row pair) of each tile: n_tiles * 16 workgroups.
 extern "C" hipError_t ptk_launch_features(const FeatArgs* a, int n_tiles, hipStream_t s);
+
+// Ray queries on the device (trace_kernel; ptgpu.h pt_trace_rays_device): n
+// rays of two float4 each, {o, tmax} and {d, unused}.  Closest mode writes two
+// float4 per ray into `rec`; occluded mode one bit per ray into `occ`, two
+// 32-bit words per chunk of 64 rays.
+struct TraceArgs {
+  const DNode* nodes;
+  const DPrim* prims;
+  const float* norms;
+  const int* prim_map;   // own BVH order -> the caller's primitive index (null: the same)
+  const float4* rays;
+  float4* rec;           // closest mode: {t, u, v, prim}, {n, bsdf} per ray
+  uint32_t* occ;         // occluded mode: ceil(n / 64) * 2 words
+  unsigned long long* counts;  // rays, hits, invalid: added to
+  int* stack_spill;      // traversal stack entries beyond PT_STACK of grid * PT_BLOCK lanes (null if the BVH never needs them)
+  long long n;
+};
+// `grid` one-wave workgroups; wave b takes the chunks b, b + grid, ... (trace_host.h trace_grid).
+extern "C" hipError_t ptk_launch_trace(const TraceArgs* a, int grid, bool occluded, hipStream_t s);
+// Resident one-wave workgroups per CU of the closest / occluded build.
+extern "C" hipError_t ptk_trace_occupancy(int* waves_per_cu, bool occluded);
+
+// Pixel-centre camera rays of the listed tiles (camera_rays_kernel; ptgpu.h
+// pt_camera_rays_device), in trace_kernel's ray layout at p = x + y * W.
+struct CamRayArgs {
+  float cam_pos[3];
+  float c2w_col0[3], c2w_col1[3], c2w_col2[3];
+  float cam_ax, cam_ay;
+  float inv_w, inv_h;
+  int W, H;
+  const int4* tiles;  // (x, y, w, h), each <= 32 x 32 and inside the frame
+  float4* rays;       // 2 * W * H
+};
+extern "C" hipError_t ptk_launch_camera_rays(const CamRayArgs* a, int n_tiles, hipStream_t s);

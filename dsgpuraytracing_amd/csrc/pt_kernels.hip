@@ -1801,11 +1801,30 @@ __global__ __launch_bounds__(PT_BLOCK) void intersect_kernel(const DNode* __rest
 }
 
 // The hit record of the shading phase (render_kernel: "hit record"), restated
-// for the feature pass: the hit point rebuilt from the primitive, the shading
-// normal interpolated and, for a triangle, flipped to face the ray.
+// for the feature pass and the ray queries: the hit point rebuilt from the
+// primitive, the shading normal interpolated and, for a triangle, flipped to
+// face the ray; hu, hv: the barycentrics (Moller-Trumbore, as mt_terms), 0 on
+// a sphere.
+// features_kernel and trace_kernel must give the same bits for the same ray,
+// so nothing here is left to the compiler's contraction of a * b + c, which
+// pairs the products of a sum differently from one inlining to the next: every
+// fused operation is written as one (the pairing is the one the feature pass
+// has always had), every other one is rounded on its own.
+__device__ __forceinline__ float fma_dot(float3 a, float3 b, int first) {
+#pragma clang fp contract(off)
+  // a . b, the product of component `first` (0 = x, 1 = y) rounded, the others fused onto it in x, y, z order
+  return first == 0 ? __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.y, b.y, a.x * b.x))
+                    : __builtin_fmaf(a.z, b.z, __builtin_fmaf(a.x, b.x, a.y * b.y));
+}
+__device__ __forceinline__ float3 fma_cross(float3 u, float3 v) {
+#pragma clang fp contract(off)
+  return f3(__builtin_fmaf(u.y, v.z, -(u.z * v.y)), __builtin_fmaf(u.z, v.x, -(u.x * v.z)),
+            __builtin_fmaf(u.x, v.y, -(u.y * v.x)));
+}
 __device__ __forceinline__ void first_hit_record(const DPrim* __restrict__ prims, const float* __restrict__ norms,
                                                  float3 o, float3 d, const Hit& h, float3& hp, float3& ns,
-                                                 int& bsdf) {
+                                                 int& bsdf, float& hu, float& hv) {
+#pragma clang fp contract(off)
   const DPrim pr = prims[h.prim];
   float nn[9];
   for (int k = 0; k < 9; ++k) nn[k] = norms[9 * (size_t)h.prim + k];
@@ -1813,17 +1832,49 @@ __device__ __forceinline__ void first_hit_record(const DPrim* __restrict__ prims
   bsdf = meta >> 1;
   if (meta & 1) {
     float3 V0 = f3(pr.v0.x, pr.v0.y, pr.v0.z), E1 = f3(pr.e1.x, pr.e1.y, pr.e1.z), E2 = f3(pr.e2.x, pr.e2.y, pr.e2.z);
-    float hu, hv, ht;
-    mt_terms(o, d, V0, E1, E2, hu, hv, ht);  // the barycentrics of the traversal test
-    float w0 = 1.0f - hu - hv;
-    hp = V0 + E1 * hu + E2 * hv;
-    ns = ld3(nn) * w0 + ld3(nn + 3) * hu + ld3(nn + 6) * hv;
-    if (dot(d, ns) > 0.0f) ns = f3(0, 0, 0) - ns;
+    const float3 pv = fma_cross(d, E2);
+    const float id = __builtin_amdgcn_rcpf(fma_dot(E1, pv, 1));
+    const float3 tv = o - V0;
+    const float du = fma_dot(tv, pv, 1), dv = fma_dot(d, fma_cross(tv, E1), 0);
+    hu = du * id;
+    hv = id * dv;
+    const float w0 = __builtin_fmaf(-id, dv, __builtin_fmaf(-du, id, 1.0f));  // 1 - hu - hv
+    const float3 n0 = ld3(nn), n1 = ld3(nn + 3), n2 = ld3(nn + 6);
+    hp = f3(__builtin_fmaf(E2.x, hv, __builtin_fmaf(E1.x, hu, V0.x)), __builtin_fmaf(E2.y, hv, __builtin_fmaf(E1.y, hu, V0.y)),
+            __builtin_fmaf(E2.z, hv, __builtin_fmaf(E1.z, hu, V0.z)));
+    ns = f3(__builtin_fmaf(n2.x, hv, __builtin_fmaf(n1.x, hu, n0.x * w0)), __builtin_fmaf(n2.y, hv, __builtin_fmaf(n1.y, hu, n0.y * w0)),
+            __builtin_fmaf(n2.z, hv, __builtin_fmaf(n1.z, hu, n0.z * w0)));
+    if (fma_dot(d, ns, 1) > 0.0f) ns = f3(0, 0, 0) - ns;
   } else {
     float3 C = f3(pr.v0.x, pr.v0.y, pr.v0.z);
-    ns = normalize(o + d * h.t - C);
-    hp = C + ns * pr.e1.x;
+    const float3 r = f3(__builtin_fmaf(d.x, h.t, o.x), __builtin_fmaf(d.y, h.t, o.y), __builtin_fmaf(d.z, h.t, o.z)) - C;
+    ns = r * __builtin_amdgcn_rsqf(fma_dot(r, r, 1));
+    hp = f3(__builtin_fmaf(pr.e1.x, ns.x, C.x), __builtin_fmaf(pr.e1.x, ns.y, C.y), __builtin_fmaf(pr.e1.x, ns.z, C.z));
+    hu = hv = 0.0f;
   }
+}
+// The record's normal: of unit length, the zero vector if it has none.
+__device__ __forceinline__ float3 unit_or_zero(float3 ns) {
+  const float l2 = fma_dot(ns, ns, 0);
+  return l2 > 0.0f ? ns * __builtin_amdgcn_rsqf(l2) : f3(0, 0, 0);
+}
+
+// The camera ray through the centre of pixel (x, y), as render_kernel's
+// camera_ray casts it without jitter: the feature pass traces it and
+// camera_rays_kernel writes it out, from this one function and, as the hit
+// record above, with every fused operation written out, so that the two agree
+// bit for bit.
+template <class A>
+__device__ __forceinline__ void pixel_centre_ray(const A& a, int x, int y, float3& o, float3& d) {
+#pragma clang fp contract(off)
+  const float sx = __builtin_fmaf(-((float)x + 0.5f), a.inv_w, 0.5f) * a.cam_ax;
+  const float sy = __builtin_fmaf(-((float)y + 0.5f), a.inv_h, 0.5f) * a.cam_ay;
+  const float3 c0 = ld3(a.c2w_col0), c1 = ld3(a.c2w_col1);
+  const float3 wsp = f3(__builtin_fmaf(c1.x, sy, c0.x * sx), __builtin_fmaf(c1.y, sy, c0.y * sx), __builtin_fmaf(c1.z, sy, c0.z * sx)) +
+                     ld3(a.c2w_col2);  // (the screen point's z is 1)
+  const float3 v = f3(0, 0, 0) - wsp;
+  d = v * __builtin_amdgcn_rsqf(fma_dot(v, v, 0));
+  o = wsp + ld3(a.cam_pos);
 }
 
 // First-hit feature records of the listed tiles (ptgpu.h: pt_render_features_device):
@@ -1835,12 +1886,8 @@ __global__ __launch_bounds__(PT_BLOCK) void features_kernel(FeatArgs A) {
   const int4 tile = A.tiles[blockIdx.x >> 4];
   const int2 px = tile_pixel(tile, (blockIdx.x & 15u) * PT_BLOCK + threadIdx.x);
   if (px.x < 0 || px.x >= A.W || px.y >= A.H) return;
-  float fx = ((float)px.x + 0.5f) * A.inv_w;
-  float fy = ((float)px.y + 0.5f) * A.inv_h;
-  float3 sp = f3((0.5f - fx) * A.cam_ax, (0.5f - fy) * A.cam_ay, 1.0f);
-  float3 wsp = ld3(A.c2w_col0) * sp.x + ld3(A.c2w_col1) * sp.y + ld3(A.c2w_col2) * sp.z;
-  const float3 d = normalize(f3(0, 0, 0) - wsp);
-  const float3 o = wsp + ld3(A.cam_pos);
+  float3 o, d;
+  pixel_centre_ray(A, px.x, px.y, o, d);
   Hit h;
   h.t = 0;
   h.prim = -1;
@@ -1850,15 +1897,115 @@ __global__ __launch_bounds__(PT_BLOCK) void features_kernel(FeatArgs A) {
   if (found) {
     float3 hp, ns;
     int bsdf;
-    first_hit_record(A.prims, A.norms, o, d, h, hp, ns, bsdf);
-    const float l2 = dot(ns, ns);
-    const float3 n = l2 > 0.0f ? ns * __builtin_amdgcn_rsqf(l2) : f3(0, 0, 0);
+    float hu, hv;
+    first_hit_record(A.prims, A.norms, o, d, h, hp, ns, bsdf, hu, hv);
+    const float3 n = unit_or_zero(ns);
     r0 = make_float4(n.x, n.y, n.z, __int_as_float(bsdf));
     r1 = make_float4(hp.x, hp.y, hp.z, h.t);
   }
   const size_t p = (size_t)px.x + (size_t)px.y * (size_t)A.W;
   A.feat[p] = r0;
   A.feat[(size_t)A.W * (size_t)A.H + p] = r1;
+}
+
+// Not finite: the exponent field is all ones (inf or NaN).
+__device__ __forceinline__ bool not_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// Ray queries from device memory (ptgpu.h: pt_trace_rays_device): one lane per
+// ray, one wave per workgroup, the grid bounded -- wave b takes the chunks of
+// 64 rays b, b + grid, b + 2 * grid, ..., so the spill area is the grid's, not
+// the ray count's.  A ray is two 16-B loads: {o, tmax}, {d, unused}.
+// Before any traversal tmax is clamped to the traversal's "not entered" mark
+// (pt_api.cpp pt_intersect: beyond it a ray enters unused BVH4 slots and may
+// walk for ever), and a ray that is not finite, has no direction or no
+// positive tmax is never traversed: it reports a miss and is counted.  So is
+// one whose origin over its direction overflows on all three axes (origins
+// beyond 1e38 for unit directions): every slab distance of an unused slot is
+// then NaN, which the min/max chain drops, and the slot would be entered.
+// OCC = false: the nearest hit in (0, tmax) as two float4, {t, u, v, prim}
+// (prim in the caller's order) and the {normal, bsdf} features_kernel writes
+// for that hit; a miss is {-1, 0, 0, -1}, {0, 0, 0, -1}.
+// OCC = true: the any-hit walk; the chunk's ballot as two 32-bit words, stored
+// by lane 0 (bits of lanes at or past n are zero: those lanes trace nothing).
+// Counters {rays, hits, invalid}: ballots and popcounts summed over the wave's
+// chunks (uniform), added by one three-lane vector atomic per wave.
+template <bool OCC>
+__global__ __launch_bounds__(PT_BLOCK) void trace_kernel(TraceArgs A) {
+  __shared__ int s_stack[PT_STACK * PT_BLOCK];
+  const Stack stk{(lds_int*)(s_stack + threadIdx.x), A.stack_spill, gridDim.x * PT_BLOCK};
+  const long long n_chunks = (A.n + (PT_BLOCK - 1)) / PT_BLOCK;
+  uint32_t n_rays = 0, n_hits = 0, n_invalid = 0;  // of the wave (uniform)
+  // (every lane takes every trip: the ballots below are whole-wave)
+#pragma unroll 1
+  for (long long ch = blockIdx.x; ch < n_chunks; ch += gridDim.x) {
+    const long long i = ch * PT_BLOCK + threadIdx.x;
+    const bool in = i < A.n;
+    float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r1 = r0;
+    if (in) {
+      r0 = A.rays[2 * i];
+      r1 = A.rays[2 * i + 1];
+    }
+    const float3 o = f3(r0.x, r0.y, r0.z), d = f3(r1.x, r1.y, r1.z);
+    const float tmax = fminf(r0.w, 3.0e38f);
+    bool valid = r0.w > 0.0f;  // (false for a NaN)
+    valid &= !(not_finite(o.x) || not_finite(o.y) || not_finite(o.z) || not_finite(d.x) || not_finite(d.y) || not_finite(d.z));
+    valid &= !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f);
+    {
+      Trav probe;  // o * (1 / d) as the node step forms it
+      trav_init(probe, o, d, tmax, OCC);
+      valid &= !(not_finite(o.x * probe.inv.x) && not_finite(o.y * probe.inv.y) && not_finite(o.z * probe.inv.z));
+    }
+    Hit h;
+    h.t = 0;
+    h.prim = -1;
+    Counters ct = {0, 0, 0};
+    bool found = false;
+    if (in && valid) found = traverse<false>(A.nodes, A.prims, stk, o, d, tmax, OCC, h, ct);
+    const unsigned long long hits = __ballot(found);
+    n_rays += (uint32_t)__popcll(__ballot(in));
+    n_hits += (uint32_t)__popcll(hits);
+    n_invalid += (uint32_t)__popcll(__ballot(in && !valid));
+    if constexpr (OCC) {
+      if (threadIdx.x == 0) *(uint2*)(A.occ + 2 * ch) = make_uint2((uint32_t)hits, (uint32_t)(hits >> 32));
+    } else {
+      float4 q0 = make_float4(-1.0f, 0.0f, 0.0f, __int_as_float(-1)), q1 = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+      if (found) {
+        float3 hp, ns;
+        int bsdf;
+        float hu, hv;
+        first_hit_record(A.prims, A.norms, o, d, h, hp, ns, bsdf, hu, hv);
+        const float3 nrm = unit_or_zero(ns);
+        const int prim = A.prim_map ? A.prim_map[h.prim] : h.prim;
+        q0 = make_float4(h.t, hu, hv, __int_as_float(prim));
+        q1 = make_float4(nrm.x, nrm.y, nrm.z, __int_as_float(bsdf));
+      }
+      if (in) {
+        A.rec[2 * i] = q0;
+        A.rec[2 * i + 1] = q1;
+      }
+    }
+  }
+  if (threadIdx.x < 3) {
+    const uint32_t v = threadIdx.x == 0 ? n_rays : threadIdx.x == 1 ? n_hits : n_invalid;
+    if (v) atomicAdd(A.counts + threadIdx.x, (unsigned long long)v);
+  }
+}
+
+// The pixel-centre camera rays of the listed tiles in trace_kernel's layout
+// (ptgpu.h: pt_camera_rays_device): features_kernel's grid and pixel order,
+// its ray (pixel_centre_ray), tmax at the traversal's mark.  (A template, as
+// trace_kernel is one, so that the compiler emits it behind the render kernels
+// and they keep their places in the code object.)
+template <int FAR_MARK = 0>
+__global__ __launch_bounds__(PT_BLOCK) void camera_rays_kernel(CamRayArgs A) {
+  const int4 tile = A.tiles[blockIdx.x >> 4];
+  const int2 px = tile_pixel(tile, (blockIdx.x & 15u) * PT_BLOCK + threadIdx.x);
+  if (px.x < 0 || px.x >= A.W || px.y >= A.H) return;
+  float3 o, d;
+  pixel_centre_ray(A, px.x, px.y, o, d);
+  const size_t p = (size_t)px.x + (size_t)px.y * (size_t)A.W;
+  A.rays[2 * p] = make_float4(o.x, o.y, o.z, 3.0e38f);
+  A.rays[2 * p + 1] = make_float4(d.x, d.y, d.z, 0.0f);
 }
 
 #endif  // !PT_ENV_TU
@@ -1984,6 +2131,27 @@ extern "C" hipError_t ptk_launch_intersect(const DNode* nodes, const DPrim* prim
 extern "C" hipError_t ptk_launch_features(const FeatArgs* a, int n_tiles, hipStream_t s) {
   if (n_tiles <= 0) return hipSuccess;
   hipLaunchKernelGGL(ptk::features_kernel, dim3((unsigned)n_tiles * 16u), dim3(PT_BLOCK), 0, s, *a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t ptk_launch_trace(const TraceArgs* a, int grid, bool occluded, hipStream_t s) {
+  if (a->n <= 0 || grid <= 0) return hipSuccess;
+  if (occluded) hipLaunchKernelGGL(ptk::trace_kernel<true>, dim3((unsigned)grid), dim3(PT_BLOCK), 0, s, *a);
+  else hipLaunchKernelGGL(ptk::trace_kernel<false>, dim3((unsigned)grid), dim3(PT_BLOCK), 0, s, *a);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t ptk_trace_occupancy(int* waves_per_cu, bool occluded) {
+  int blocks = 0;
+  hipError_t e = occluded ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, ptk::trace_kernel<true>, PT_BLOCK, 0)
+                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, ptk::trace_kernel<false>, PT_BLOCK, 0);
+  *waves_per_cu = blocks;
+  return e;
+}
+
+extern "C" hipError_t ptk_launch_camera_rays(const CamRayArgs* a, int n_tiles, hipStream_t s) {
+  if (n_tiles <= 0) return hipSuccess;
+  hipLaunchKernelGGL(ptk::camera_rays_kernel<>, dim3((unsigned)n_tiles * 16u), dim3(PT_BLOCK), 0, s, *a);
   return hipGetLastError();
 }
 

@@ -27,6 +27,7 @@ PT_FLAG_REF_COUNTS = 2
 PT_FLAG_PACKED = 4
 PT_FLAG_PACKED16 = 8
 PT_MAX_FRAMES = 8  # frames per pt_render_frames_device launch (include/ptgpu.h)
+PT_TRACE_CLOSEST, PT_TRACE_OCCLUDED = 0, 1  # modes of pt_trace_rays*
 
 PRIM_SPHERE, PRIM_TRIANGLE = 0, 1
 BSDF_DIFFUSE, BSDF_MIRROR, BSDF_REFRACTION, BSDF_GLASS, BSDF_EMISSION = range(5)
@@ -121,6 +122,10 @@ class pt_reproject_info(ctypes.Structure):
     _fields_ = [("kept", c_int64), ("reset", c_int64), ("reproject_ms", c_double)]
 
 
+class pt_trace_info(ctypes.Structure):
+    _fields_ = [("rays", c_int64), ("hits", c_int64), ("invalid", c_int64), ("trace_ms", c_double)]
+
+
 class pt_bvh_info(ctypes.Structure):
     _fields_ = [("n_prims", c_int64), ("n_nodes4", c_int64), ("n_nodes2", c_int64), ("bvh_stack", c_int32),
                 ("has_prim_map", c_int32), ("root_lo", c_float * 3), ("root_hi", c_float * 3)]
@@ -178,6 +183,10 @@ _SIGS = {
     "pt_debug_film_records": (c_int32, [c_void_p, POINTER(c_void_p)]),
     "pt_render_features_device": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p, c_void_p]),
     "pt_render_features": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p]),
+    "pt_trace_rays_device": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_void_p]),
+    "pt_trace_rays": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32]),
+    "pt_camera_rays_device": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p, c_void_p]),
+    "pt_get_trace_info": (c_int32, [c_void_p, POINTER(pt_trace_info)]),
     "pt_denoise_params_default": (c_int32, [POINTER(pt_denoise_params)]),
     "pt_denoise_device": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(pt_denoise_params), c_void_p,
                                     c_void_p]),

@@ -265,6 +265,128 @@ class Device:
         check(self._lib.pt_render_features_device(self.handle, arr, len(keep), ctypes.c_void_p(feat_ptr or None),
                                                   ctypes.c_void_p(stream or None)))
 
+    _TRACE_MODES = {"closest": native.PT_TRACE_CLOSEST, "occluded": native.PT_TRACE_OCCLUDED}
+
+    @staticmethod
+    def _trace_records(rec: np.ndarray) -> dict:
+        """The (n, 8) float32 closest-hit records as named views."""
+        return {"t": rec[:, 0], "u": rec[:, 1], "v": rec[:, 2], "prim": rec[:, 3].view(np.int32),
+                "normal": rec[:, 4:7], "bsdf": rec[:, 7].view(np.int32), "records": rec}
+
+    def trace_rays(self, rays, mode: str = "closest", out=None, stream: int = 0):
+        """Casts the caller's rays through the uploaded scene (pt_trace_rays*).
+        `rays` is (n, 8) float32: {o.x, o.y, o.z, tmax, d.x, d.y, d.z, unused},
+        d of unit length.
+
+        A numpy array goes through the host call, which waits: "closest"
+        returns the dict {"t", "u", "v", "prim", "normal", "bsdf", "records"}
+        of views of the (n, 8) float32 record array (a miss: t = -1, prim =
+        bsdf = -1), "occluded" a boolean (n,) mask.
+
+        An object with data_ptr() on the device (a torch tensor; torch is
+        imported only then) goes to the device entry point, queued on `stream`
+        (default: torch's current stream): "closest" returns the (n, 8)
+        float32 record tensor, "occluded" the packed int32 words (ceil(n / 64)
+        * 2; ray i is bit i % 32 of word i // 32), on the rays' device.  `out`
+        is the array or tensor to write instead of a new one."""
+        if mode not in self._TRACE_MODES:
+            raise ValueError(f"trace_rays: mode must be 'closest' or 'occluded', got {mode!r}")
+        m = self._TRACE_MODES[mode]
+        if hasattr(rays, "data_ptr"):
+            return self._trace_rays_torch(rays, m, out, stream)
+        rays = np.ascontiguousarray(rays, np.float32)
+        if rays.ndim != 2 or rays.shape[1] != 8:
+            raise ValueError(f"trace_rays: need an (n, 8) float32 array, got {rays.shape}")
+        n = len(rays)
+        words = (n + 63) // 64 * 2
+        shape, dtype = ((n, 8), np.float32) if m == native.PT_TRACE_CLOSEST else ((words,), np.uint32)
+        if out is None:
+            out = np.zeros(shape, dtype)
+        elif out.dtype != dtype or out.shape != shape or not out.flags.c_contiguous:
+            raise ValueError(f"trace_rays: out must be a C-contiguous {np.dtype(dtype).name} array of shape {shape}")
+        check(self._lib.pt_trace_rays(self.handle, n, rays.ctypes.data if n else None, out.ctypes.data if n else None, m))
+        if m == native.PT_TRACE_CLOSEST:
+            return self._trace_records(out)
+        return np.unpackbits(out.view(np.uint8), bitorder="little")[:n].astype(bool)
+
+    def _trace_rays_torch(self, rays, m: int, out, stream: int):
+        import torch
+        if (not rays.is_cuda or rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8
+                or not rays.is_contiguous()):
+            raise ValueError("trace_rays: need a contiguous (n, 8) float32 tensor on the device")
+        if rays.device.index != self.device:
+            raise ValueError(f"trace_rays: the rays are on {rays.device}, the context on device {self.device}")
+        n = rays.shape[0]
+        words = (n + 63) // 64 * 2
+        shape, dtype = ((n, 8), torch.float32) if m == native.PT_TRACE_CLOSEST else ((words,), torch.int32)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=rays.device)
+        elif (out.device != rays.device or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError(f"trace_rays: out must be a contiguous {dtype} tensor of shape {shape} on {rays.device}")
+        self._on_torch_stream(rays.device, stream, lambda s: check(self._lib.pt_trace_rays_device(
+            self.handle, n, ctypes.c_void_p(rays.data_ptr() if n else None), ctypes.c_void_p(out.data_ptr() if n else None),
+            m, ctypes.c_void_p(s))))
+        return out
+
+    def _on_torch_stream(self, device, stream: int, call):
+        """Runs call(stream handle) in the order of `stream`, or of torch's
+        current stream of `device`.  The library takes a NULL stream for the
+        context's own, so torch's default stream (handle 0) cannot be handed
+        over: the call then runs on a side stream of this Device that waits
+        for the default stream and that the default stream waits for."""
+        import torch
+        if stream:
+            return call(stream)
+        cur = torch.cuda.current_stream(device)
+        if cur.cuda_stream:
+            return call(cur.cuda_stream)
+        side = getattr(self, "_torch_side", None)
+        if side is None:
+            side = self._torch_side = torch.cuda.Stream(device)
+        side.wait_stream(cur)
+        call(side.cuda_stream)
+        cur.wait_stream(side)
+
+    def camera_rays(self, tiles=None, out=None, stream: int = 0):
+        """The pixel-centre camera rays render_features traces, of `tiles` (the
+        whole frame by default), at row x + y * W of an (H * W, 8) float32 ray
+        buffer as trace_rays takes it (pt_camera_rays_device).  Without `out`
+        (or with a numpy array) the result is a numpy array, rows outside the
+        tiles left as they were (zero in a new one), and the call waits; a
+        device tensor `out` is filled on `stream` (default: torch's current
+        stream) and returned."""
+        hw = getattr(self, "_frame", None)
+        if hw is None:
+            raise ValueError("camera_rays: set_params first")
+        h, w = hw
+        keep, arr = self._tiles(tile_fifo(w, h) if tiles is None else tiles)
+        if out is not None and hasattr(out, "data_ptr"):
+            import torch
+            if (not out.is_cuda or out.device.index != self.device or out.dtype != torch.float32
+                    or tuple(out.shape) != (h * w, 8) or not out.is_contiguous()):
+                raise ValueError(f"camera_rays: out must be a contiguous float32 tensor of shape {(h * w, 8)} on device "
+                                 f"{self.device}")
+            self._on_torch_stream(out.device, stream, lambda s: check(self._lib.pt_camera_rays_device(
+                self.handle, arr, len(keep), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(s))))
+            return out
+        import torch  # (the numpy form stages through a torch tensor: the library hands out no device memory)
+        if out is None:
+            out = np.zeros((h * w, 8), np.float32)
+        elif out.dtype != np.float32 or out.shape != (h * w, 8) or not out.flags.c_contiguous:
+            raise ValueError(f"camera_rays: out must be a C-contiguous float32 array of shape {(h * w, 8)}")
+        dev = torch.device("cuda", self.device)
+        t = torch.from_numpy(out).to(dev)
+        self._on_torch_stream(dev, 0, lambda s: check(self._lib.pt_camera_rays_device(
+            self.handle, arr, len(keep), ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(s))))
+        out[...] = t.cpu().numpy()
+        return out
+
+    def trace_info(self) -> dict:
+        """pt_get_trace_info: {rays, hits, invalid, trace_ms} of the last trace (waits for it)."""
+        i = native.pt_trace_info()
+        check(self._lib.pt_get_trace_info(self.handle, ctypes.byref(i)))
+        return {"rays": int(i.rays), "hits": int(i.hits), "invalid": int(i.invalid), "trace_ms": float(i.trace_ms)}
+
     def stats(self) -> dict:
         s = native.pt_stats()
         check(self._lib.pt_get_stats(self.handle, ctypes.byref(s)))

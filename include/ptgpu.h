@@ -50,6 +50,9 @@
  *                               pixel): films of a multi-GPU tile or sample split, checkpoints
  *   pt_render_features*         no counterpart: the camera ray's Intersection (trace_ray,
  *                               pathtracer.cpp:435-456) kept per pixel: normal, hit point, depth, BSDF
+ *   pt_trace_rays* / pt_camera_rays_device   BVHAccel::intersect (src/bvh.cpp:331-362) for rays
+ *                               and results in device memory, in stream order: closest-hit
+ *                               records or occlusion bits; the feature pass's camera rays
  *   pt_denoise_* / pt_film_denoise*   no counterpart: an edge-avoiding filter of the film's mean,
  *                               guided by those records and the film's variance
  *   pt_reproject_* / pt_film_reproject   no counterpart: the film kept across a camera move, its
@@ -592,6 +595,59 @@ int pt_debug_film_records(pt_film* film, void** rec_dev);
 int pt_render_features_device(pt_ctx* ctx, const pt_tile* tiles, int32_t n_tiles, void* feat_dev, void* stream);
 /* The same into a host buffer of 2*width*height*16 bytes; waits. */
 int pt_render_features(pt_ctx* ctx, const pt_tile* tiles, int32_t n_tiles, void* feat_host);
+
+/* ---- Ray queries on the device (BVHAccel::intersect, src/bvh.cpp:331-362, for
+ * rays and results that live in device memory, in stream order; pt_intersect
+ * stays the host-side diagnostic).  A ray is 32 bytes, two float4:
+ *   ray[2i]     = {o.x, o.y, o.z, tmax}
+ *   ray[2i + 1] = {d.x, d.y, d.z, unused}
+ * d is of unit length (the caller's contract, as pt_intersect's: it is neither
+ * checked nor normalised).  tmax is clamped to 3.0e38, the traversal's "far",
+ * so +inf is welcome.  A ray is INVALID, is never traversed, reports a miss /
+ * unoccluded and is counted in pt_trace_info.invalid when a component of o or
+ * d is not finite, d is all zero, tmax is NaN or <= 0, or o over d overflows
+ * f32 on all three axes (origins beyond 1e38 at unit directions).
+ *
+ * PT_TRACE_CLOSEST: the nearest hit in (0, tmax), 32 bytes per ray:
+ *   out[2i]     = {t, u, v, prim}        f32 f32 f32 i32
+ *   out[2i + 1] = {N.x, N.y, N.z, bsdf}  f32 f32 f32 i32
+ * prim is the primitive's index in the caller's order (whatever tree renders),
+ * u and v the triangle test's barycentrics (0 on a sphere), {N, bsdf} the
+ * feature record pt_render_features* writes for that hit.  A miss is
+ * {-1, 0, 0, -1} and {0, 0, 0, -1}.
+ * PT_TRACE_OCCLUDED: whether anything lies in (0, tmax), one bit per ray: ray
+ * i is bit i % 32 of the uint32 word i / 32.  The output is ceil(n / 64) * 2
+ * words; bits at or past n are written as zero.
+ *
+ * pt_trace_rays_device queues the kernel on `stream` (NULL: the context's) and
+ * returns; the results are in stream order (pt_render_features_device's
+ * semantics).  n == 0 is PT_OK and launches nothing.  PT_E_INVALID: a NULL
+ * context or buffer, n < 0 or > 2^40, an unknown mode, ray and output ranges
+ * that overlap; PT_E_NOSCENE before pt_upload_scene.  The grid is bounded by
+ * what the device holds at once (and by the environment variable
+ * PT_TRACE_WAVES, read at each call: a testing knob), each wave taking every
+ * grid-th chunk of 64 rays; the context's spill area and counter are reused
+ * from call to call, and a trace on another stream than the last waits for it. */
+#define PT_TRACE_CLOSEST 0
+#define PT_TRACE_OCCLUDED 1
+typedef struct pt_trace_info {
+  int64_t rays, hits, invalid; /* of the last trace: rays given, hits / occluded rays, invalid rays */
+  double trace_ms;             /* its kernel, between HIP events */
+} pt_trace_info;
+int pt_trace_rays_device(pt_ctx* ctx, int64_t n, const void* rays_dev, void* out_dev, int32_t mode, void* stream);
+/* The same from and into host buffers: stages, waits. */
+int pt_trace_rays(pt_ctx* ctx, int64_t n, const void* rays_host, void* out_host, int32_t mode);
+/* The ray pt_render_features* traces through the centre of each pixel of the
+ * listed tiles (clipped to the frame), written at ray[2p], p = x + y*W, of a
+ * buffer of width*height rays, with tmax = 3.0e38; pixels outside the tiles
+ * are left alone.  Frame size, scene and camera are the context's
+ * (PT_E_NOSCENE before pt_upload_scene / pt_set_camera / pt_set_params);
+ * PT_E_INVALID for a NULL context or buffer or n_tiles < 0.  Queued on
+ * `stream`. */
+int pt_camera_rays_device(pt_ctx* ctx, const pt_tile* tiles, int32_t n_tiles, void* rays_dev, void* stream);
+/* Of the context's last trace (all zero before the first, and after one of
+ * n == 0); waits for it. */
+int pt_get_trace_info(pt_ctx* ctx, pt_trace_info* out);
 
 /* ---- Denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010)
  * guided by the feature records and, as the spatial pass of SVGF, by the
