@@ -1,7 +1,7 @@
 """Builds the in-tree native library ``libptgpu.so`` for gfx950 with hipcc.
 
 The library holds the HIP kernels (csrc/pt_kernels.hip), the C ABI
-(csrc/pt_api.cpp, csrc/pt_api_film.cpp and csrc/pt_api_trace.cpp over the context of csrc/pt_ctx.h;
+(csrc/pt_api.cpp, csrc/pt_api_film.cpp, csrc/pt_api_trace.cpp and csrc/pt_api_rays.cpp over the context of csrc/pt_ctx.h;
 include/ptgpu.h), the asynchronous tile seam (csrc/tile_seam.cpp), the host
 flattening of an uploaded scene (csrc/scene_flatten.cpp) and the native host
 scene pipeline (csrc/scene_host.cpp).  Only the pt_api*.cpp units and the .hip

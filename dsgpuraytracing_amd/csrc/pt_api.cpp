@@ -231,8 +231,11 @@ int build_tiles(pt_ctx* c, const pt_tile* tiles, int32_t n, std::vector<int4>& o
 }
 
 // What the launch policy (launch_plan.h) reads of the context, for `nf` frames of the tiles `tl`.
+// A ray launch (`rays`) has no camera: no screen footprint culls its pixels or
+// sizes its sample groups, its kernel has no triangle-only or pixel-trace
+// build, and its grid follows the RAYS builds' own occupancy.
 static PlanInput plan_input(const pt_ctx* c, const std::vector<int4>& tl, int nf, uint32_t flags, bool gpu_idle,
-                            const LaunchKnobs& knobs) {
+                            const LaunchKnobs& knobs, bool rays = false) {
   PlanInput in;
   in.W = c->params.width;
   in.H = c->params.height;
@@ -258,6 +261,14 @@ static PlanInput plan_input(const pt_ctx* c, const std::vector<int4>& tl, int nf
   in.flags = flags;
   in.gpu_idle = gpu_idle;
   in.knobs = knobs;
+  if (rays) {
+    in.cam = pt_camera{};
+    in.knobs.no_footprint_cull = true;
+    in.knobs.no_tri_only = true;
+    in.knobs.debug_x = in.knobs.debug_y = -1;
+    std::copy(c->bpc_rays, c->bpc_rays + 4, in.bpc_variant);
+    in.grid_plain = std::max(8, c->bpc_rays[0]) * c->n_cu;
+  }
   return in;
 }
 
@@ -335,8 +346,11 @@ static KParams kernel_params(const pt_ctx* c, const LaunchPlan& plan, int nf, co
 // The launch's shape -- tile order, blocks, sample groups, grid, queue claims --
 // is plan_launch's (launch_plan.cpp), from the knobs and the idle query; a
 // plan that is refused returns before anything is enqueued or any slot taken.
+// `rays`: a ray launch -- the RAYS kernel replays the caller's rays or captures
+// into them; its render stream first waits for what `s` held at the call, so
+// the rays are read (and written) in the caller's stream order.
 int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs, int nf, const uint32_t* seeds,
-                  hipStream_t s, uint32_t flags) {
+                  hipStream_t s, uint32_t flags, const RayLaunch* rays) {
   std::memset(&c->last, 0, sizeof(c->last));
   c->times_pending = false;
   if (tl_in.empty()) return PT_OK;
@@ -358,7 +372,9 @@ int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs, int nf
       return fail(PT_E_HIP, std::string("render: an earlier launch failed: ") + hipGetErrorString(q));
     }
   }
-  const LaunchPlan plan = plan_launch(plan_input(c, tl_in, nf, flags, gpu_idle, knobs));
+  if (rays && c->bpc_rays[0] <= 0)
+    for (int v = 0; v < 4; ++v) HIPCHK(ptk_render_occupancy_rays(&c->bpc_rays[v], (v & 2) != 0, (v & 1) != 0));
+  const LaunchPlan plan = plan_launch(plan_input(c, tl_in, nf, flags, gpu_idle, knobs, rays != nullptr));
   if (!plan.error.empty()) return fail(PT_E_INVALID, plan.error);
   // PT_PIPELINE=0 and census launches: every render on the caller's stream, one slot
   const bool pipelined = knobs.pipeline && !plan.census;
@@ -370,6 +386,11 @@ int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs, int nf
   hipStream_t rs = pipelined && !idle ? (hipStream_t)slot.stream : s;
   // the slot's device state is free once the previous resolve that read it ran
   if (!idle) HIPCHK(hipStreamWaitEvent(rs, slot.ev_free, 0));
+  if (rays && rs != s) {  // the rays are the caller's: everything queued on `s` so far comes first
+    HIPCHK(slot.ev_rays.create(hipEventDisableTiming));
+    HIPCHK(hipEventRecord(slot.ev_rays, s));
+    HIPCHK(hipStreamWaitEvent(rs, slot.ev_rays, 0));
+  }
   const PlanRect* tl = plan.zorder ? plan.ztiles.data() : reinterpret_cast<const PlanRect*>(tl_in.data());
   const bool tile_out = plan.zorder && (flags & (PT_FLAG_PACKED | PT_FLAG_PACKED16));  // packed outputs keep the caller's tile index
   HIPCHK(slot.tiles.sync(tl, tl_in.size(), rs));
@@ -396,6 +417,8 @@ int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs, int nf
   P.tile_out = tile_out ? slot.tout.dev.p : nullptr;
   P.blocks = slot.blocks.dev.p;
   P.tile_block0 = slot.tblock0.dev.p;
+  P.rays = rays ? rays->rays : nullptr;
+  P.rays_capture = rays && rays->capture ? 1 : 0;
   // (growing a buffer synchronises the device: a frame batch sizes every render slot's at once)
   if (nf > 1)
     for (RenderSlot& k : c->slots) {

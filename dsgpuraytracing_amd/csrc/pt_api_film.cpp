@@ -96,30 +96,39 @@ int pt_film_set_next_sample(pt_film* f, uint32_t next_sample) {
   return PT_OK;
 }
 
-int pt_film_add_pass(pt_film* f, const pt_tile* tiles, int32_t n_tiles, void* stream) {
-  if (!f) return fail(PT_E_INVALID, "pt_film_add_pass: NULL film");
+// pt_film_add_pass, and with `rays_dev` pt_film_add_pass_rays: the pass rendered
+// by replay of the caller's rays (which needs no camera).
+static int film_add_pass(pt_film* f, const pt_tile* tiles, int32_t n_tiles, const void* rays_dev, bool by_rays,
+                         void* stream) {
+  const std::string fn = by_rays ? "pt_film_add_pass_rays" : "pt_film_add_pass";
+  if (!f) return fail(PT_E_INVALID, fn + ": NULL film");
   pt_ctx* c = f->ctx;
-  int rc = check_ready(c);
-  if (rc) return rc;
-  if (n_tiles < 0 || (n_tiles > 0 && !tiles)) return fail(PT_E_INVALID, "pt_film_add_pass: bad args");
+  int rc = PT_OK;
+  if (!by_rays) {
+    if ((rc = check_ready(c))) return rc;
+  } else if (!c->have_scene || !c->have_params) {
+    return fail(PT_E_NOSCENE, "pt_film_add_pass_rays before pt_upload_scene / pt_set_params");
+  }
+  if (n_tiles < 0 || (n_tiles > 0 && !tiles)) return fail(PT_E_INVALID, fn + ": bad args");
+  if (by_rays && !rays_dev) return fail(PT_E_INVALID, fn + ": NULL ray buffer");
   const pt_params& P = c->params;
   if (P.width != f->W || P.height != f->H)
-    return fail(PT_E_INVALID, "pt_film_add_pass: pt_params frame " + std::to_string(P.width) + " x " +
+    return fail(PT_E_INVALID, fn + ": pt_params frame " + std::to_string(P.width) + " x " +
                                   std::to_string(P.height) + " differs from the film's " + std::to_string(f->W) + " x " +
                                   std::to_string(f->H));
   if (f->next + (uint64_t)P.spp > (uint64_t)1 << 32)
-    return fail(PT_E_INVALID, "pt_film_add_pass: sample range overflow (next sample " + std::to_string(f->next) +
+    return fail(PT_E_INVALID, fn + ": sample range overflow (next sample " + std::to_string(f->next) +
                                   " + spp " + std::to_string(P.spp) + " > 2^32)");
   std::vector<int4> rects;
   for (int32_t i = 0; i < n_tiles; ++i) {
     const pt_tile& t = tiles[i];
-    if (t.w < 0 || t.h < 0) return fail(PT_E_INVALID, "pt_film_add_pass: negative tile size");
+    if (t.w < 0 || t.h < 0) return fail(PT_E_INVALID, fn + ": negative tile size");
     const int x0 = std::max(0, t.x), y0 = std::max(0, t.y);
     const int x1 = (int)std::min<int64_t>(f->W, (int64_t)t.x + t.w), y1 = (int)std::min<int64_t>(f->H, (int64_t)t.y + t.h);
     if (x1 > x0 && y1 > y0) rects.push_back(make_int4(x0, y0, x1, y1));
   }
   if (!rects_disjoint(rects))
-    return fail(PT_E_INVALID, "pt_film_add_pass: tiles overlap (their samples would be counted twice)");
+    return fail(PT_E_INVALID, fn + ": tiles overlap (their samples would be counted twice)");
   if ((rc = tile_launch(c))) return rc;  // earlier asynchronous tiles first (call order)
   HIPCHK(hipSetDevice(c->device));
   // the same <= 32x32 pieces the render resolves (build_tiles of the clipped rectangles)
@@ -134,7 +143,8 @@ int pt_film_add_pass(pt_film* f, const pt_tile* tiles, int32_t n_tiles, void* st
   const uint32_t base = c->params.sample_base;
   c->params.sample_base = (uint32_t)f->next;
   float* pass = f->pass.p;
-  rc = launch(c, tl, &pass, 1, nullptr, s, 0);
+  const RayLaunch rl{(float4*)const_cast<void*>(rays_dev), false};
+  rc = launch(c, tl, &pass, 1, nullptr, s, 0, by_rays ? &rl : nullptr);
   c->params.sample_base = base;
   if (rc) return rc;
   if ((rc = finish_stats(c, s, 0, false))) return rc;
@@ -155,6 +165,14 @@ int pt_film_add_pass(pt_film* f, const pt_tile* tiles, int32_t n_tiles, void* st
   ++f->passes;
   HIPCHK(f->order.end(s));
   return PT_OK;
+}
+
+int pt_film_add_pass(pt_film* f, const pt_tile* tiles, int32_t n_tiles, void* stream) {
+  return film_add_pass(f, tiles, n_tiles, nullptr, false, stream);
+}
+
+int pt_film_add_pass_rays(pt_film* f, const pt_tile* tiles, int32_t n_tiles, const void* rays_dev, void* stream) {
+  return film_add_pass(f, tiles, n_tiles, rays_dev, true, stream);
 }
 
 int pt_film_resolve_device(pt_film* f, float* hdr_dev, uint32_t* rgba_dev, float* err_dev, void* stream) {

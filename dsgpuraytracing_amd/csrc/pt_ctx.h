@@ -89,6 +89,9 @@ struct DeviceScene {
 struct RenderSlot {
   Stream stream;
   Event ev_free;
+  // a ray launch reads the caller's rays: its render stream waits for what the
+  // caller's stream held at the call (created at the slot's first ray launch)
+  Event ev_rays;
   DevList<int4, PlanRect> tiles;
   DevList<int4, PlanRect> blocks;  // footprint-clipped 8x8 pixel blocks of the tiles
   DevList<int> tblock0;            // first block of each tile (+ the end), for the resolve
@@ -181,6 +184,11 @@ struct pt_ctx {
   int bpc_trace[2] = {0, 0};  // resident one-wave workgroups per CU: closest, occluded (asked for at first use)
   DevList<int4> cr_tiles;
   StreamOrder cr_order;
+  // ray launches (pt_render_rays*): resident waves per CU of the RAYS builds,
+  // [env * 2 + gtab] as bpc_variant (asked for at the first ray launch), and
+  // the device side of the host entry point's rays
+  int bpc_rays[4] = {0, 0, 0, 0};
+  DevBuf<float4> rr_rays;
   // Every member frees itself, in reverse order of declaration; only what
   // needs ordering is done here: no kernel may still be running when the
   // first member goes.
@@ -255,6 +263,12 @@ int build_tiles(pt_ctx* c, const pt_tile* tiles, int32_t n, std::vector<int4>& o
 // the frame in <= 32x32 pieces into `tl`, and the stream to run on.
 int render_begin(pt_ctx* c, const pt_tile* tiles, int32_t n_tiles, const char* bad_args, void* stream,
                  std::vector<int4>& tl, hipStream_t* s);
+// A ray launch (pt_render_rays*, pt_film_add_pass_rays): the W * H rays on the
+// device that the render replays, or captures into.
+struct RayLaunch {
+  float4* rays;
+  bool capture;
+};
 int launch(pt_ctx* c, const std::vector<int4>& tl_in, float* const* outs, int nf, const uint32_t* seeds, hipStream_t s,
-           uint32_t flags);
+           uint32_t flags, const RayLaunch* rays = nullptr);
 int finish_stats(pt_ctx* c, hipStream_t s, uint32_t flags, bool sync);

@@ -148,6 +148,13 @@ struct KParams {
   uint32_t frame_slots;
   uint32_t frm_m, frm_sh;  // fastdiv by frame_slots
   uint32_t seeds[PT_MAX_FRAMES];
+  // Ray launch (pt_render_rays*, the RAYS kernel; appended, so that every
+  // field above keeps its offset): W * H rays of two float4 in trace_kernel's
+  // layout, ray p = x + y * W at rays[2p].  Replay: every sample of pixel p
+  // follows ray p.  Capture (rays_capture != 0, spp 1): the camera ray of each
+  // sample is generated as ever and stored there.  Other launches: unused.
+  float4* rays;
+  int rays_capture;
 };
 
 // pt_tuning.h pt_fastdiv_init's division, on the device
@@ -183,6 +190,7 @@ extern "C" hipError_t ptk_launch_intersect(const DNode* nodes, const DPrim* prim
                                            const float* maxt, int64_t n, int32_t* hit, float* t, int32_t* prim,
                                            int32_t* anyhit, int* spill, const int* prim_map, hipStream_t s);
 extern "C" hipError_t ptk_render_occupancy(int* waves_per_cu, bool stats, bool env, bool gtab);
+extern "C" hipError_t ptk_render_occupancy_rays(int* waves_per_cu, bool env, bool gtab);  // the RAYS builds (P->rays set)
 
 // Environment-light probe (env_probe_kernel; ptgpu.h pt_debug_env_probe): the
 // env_* fields as KParams names them -- env_sample, env_uv and env_dir are

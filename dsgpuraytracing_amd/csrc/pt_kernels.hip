@@ -599,6 +599,27 @@ __device__ __forceinline__ bool box_hit(const Trav& tr, const T* lo, const T* hi
   return tn <= tf;
 }
 
+// Not finite: the exponent field is all ones (inf or NaN).
+__device__ __forceinline__ bool not_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// Whether a caller's ray {o, tmax}, {d} may be traversed (trace_kernel and the
+// RAYS render kernel: ptgpu.h calls the others INVALID).  Not one with a
+// component that is not finite, without a direction or without a positive
+// tmax (false for a NaN), and not one whose origin over its direction
+// overflows on all three axes (origins beyond 1e38 for unit directions): every
+// slab distance of an unused BVH4 slot is then NaN, which the min/max chain
+// drops, and the slot would be entered -- such a ray can walk unused slots
+// for ever.  o * (1 / d) is formed as the node step forms it (trav_init).
+__device__ __forceinline__ bool ray_query_valid(float3 o, float3 d, float tmax) {
+  bool valid = tmax > 0.0f;  // (false for a NaN)
+  valid &= !(not_finite(o.x) || not_finite(o.y) || not_finite(o.z) || not_finite(d.x) || not_finite(d.y) || not_finite(d.z));
+  valid &= !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f);
+  Trav probe;
+  trav_init(probe, o, d, tmax, false);
+  valid &= !(not_finite(o.x * probe.inv.x) && not_finite(o.y * probe.inv.y) && not_finite(o.z * probe.inv.z));
+  return valid;
+}
+
 // ---- EnvironmentLight (src/static_scene/environment_light.cpp), fp32.
 // sample_dir (130-199): lat-long bilinear lookup at texel coordinates (tu,
 // tv), wrapping in both directions exactly as the reference does.
@@ -720,7 +741,11 @@ enum : int { S_HIT = 0, S_NEE = 1, S_BSDF = 2, S_FETCH = 3, S_CAMERA = 4, S_TRAV
 // MF: a frame batch (KParams.n_frames frames of one tile set in one launch,
 // plain common build only): the queue runs over every frame's work slots, so
 // a small frame's drain is filled by the next frame's slots.
-template <bool STATS, bool DBG, bool BIN, bool ENV, bool GTAB, bool TRI = false, bool MF = false>
+// RAYS: a ray launch (ptgpu.h: pt_render_rays*; plain builds without TRI or MF
+// only): the camera-ray step loads pixel p's ray from KParams.rays instead of
+// generating it (replay), or generates it and stores it there (capture).
+// Everything after that step is the code of the other builds.
+template <bool STATS, bool DBG, bool BIN, bool ENV, bool GTAB, bool TRI = false, bool MF = false, bool RAYS = false>
 __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_PER_SIMD) void render_kernel(KParams P) {
   // the wave's PT_STACK x 64 LDS stack (lane-contiguous rows)
   __shared__ int s_stack[PT_STACK * PT_BLOCK];
@@ -891,6 +916,13 @@ __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_PER_SIMD) void render_kernel
   // (pathtracer.cpp:571-575); starts the sample's random stream.  Returns
   // whether the ray enters the scene's root box (a ray that misses it sees
   // nothing but the environment: pathtracer.cpp:421-426).
+  bool ray_bad = false;  // (RAYS) the ray just loaded may not be traversed: a miss that does not see the map either
+  // (RAYS) tmax of the extension ray parked in (hp, ns) behind a shadow ray: a
+  // bounce ray's is the far mark, a replayed camera ray's is the caller's --
+  // what the ray restarts with, at both places where a parked ray restarts
+  // (follow_on, the drain helpers' owner).  The other builds park nothing but
+  // far-mark rays and keep the constant.
+  float park_tmax = 3.0e38f;
   auto camera_ray = [&](Trav& t, float3& d) -> bool {
     const int px = pix & 0xffff, py = (int)((uint32_t)pix >> 16);
     uint32_t seed = P.seed;
@@ -904,15 +936,63 @@ __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_PER_SIMD) void render_kernel
     rdim = ptrng::kDrawInit;
     float ry = PT_DRAW();  // UniformGridSampler2D draws y first
     float rx = PT_DRAW();
-    float fx = ((float)px + rx) * P.inv_w;
-    float fy = ((float)py + ry) * P.inv_h;
-    float3 sp = f3((0.5f - fx) * P.cam_ax, (0.5f - fy) * P.cam_ay, 1.0f);
-    float3 wsp = ld3(P.c2w_col0) * sp.x + ld3(P.c2w_col1) * sp.y + ld3(P.c2w_col2) * sp.z;
-    d = normalize(f3(0, 0, 0) - wsp);
-    trav_init(t, wsp + ld3(P.cam_pos), d, 3.0e38f, false);
-    if (STATS) n_cam++;
-    if (DBG && pix_index(pix) == P.dbg_pix) printf("pixel (%d,%d) sample %d o=(%.9g %.9g %.9g) d=(%.9g %.9g %.9g)\n", px, py, sample, t.o.x, t.o.y, t.o.z, d.x, d.y, d.z);
-    return box_hit(t, P.root_lo, P.root_hi);
+    // the pinhole camera's ray through the jittered position
+    auto pinhole = [&](float3& o) {
+      float fx = ((float)px + rx) * P.inv_w;
+      float fy = ((float)py + ry) * P.inv_h;
+      float3 sp = f3((0.5f - fx) * P.cam_ax, (0.5f - fy) * P.cam_ay, 1.0f);
+      float3 wsp;
+      if constexpr (RAYS) {
+        // (capture) With contraction on, the compiler pairs the products of
+        // c0 * x + c1 * y differently from one instantiation to the next: left
+        // to itself it fused fma(c0, x, c1 * y) here, where every other build
+        // has fma(c1, y, c0 * x), and a camera that is not axis-aligned gave
+        // rays one ulp off the renderer's.  Spelled out in their pairing
+        // (the screen point's z is 1: c2 is added as it is).
+#pragma clang fp contract(off)
+        const float3 c0 = ld3(P.c2w_col0), c1 = ld3(P.c2w_col1), c2 = ld3(P.c2w_col2);
+        wsp = f3(__builtin_fmaf(c1.x, sp.y, c0.x * sp.x) + c2.x, __builtin_fmaf(c1.y, sp.y, c0.y * sp.x) + c2.y,
+                 __builtin_fmaf(c1.z, sp.y, c0.z * sp.x) + c2.z);
+      } else {
+        wsp = ld3(P.c2w_col0) * sp.x + ld3(P.c2w_col1) * sp.y + ld3(P.c2w_col2) * sp.z;
+      }
+      d = normalize(f3(0, 0, 0) - wsp);
+      o = wsp + ld3(P.cam_pos);
+    };
+    if constexpr (RAYS) {
+      // A ray launch: the ray of pixel p is ray[2p], ray[2p + 1] (two 16-B
+      // accesses).  Replay loads it -- the jitter draws above are taken and
+      // dropped, so every later draw keeps its dimension -- with tmax clamped
+      // to the traversal's "far" for this first segment; a ray that may not be
+      // traversed (ray_query_valid) becomes a harmless one that is reported
+      // as a miss which sees nothing (ray_bad).  Capture generates the camera
+      // ray and stores it.  Both arms end in the one trav_init / box_hit
+      // below, so the replay of a captured ray repeats capture's instructions.
+      float4* const rp = P.rays + 2 * (size_t)(px + py * P.W);
+      float3 o;
+      float tmax = 3.0e38f;
+      ray_bad = false;
+      if (P.rays_capture) {
+        pinhole(o);
+        rp[0] = make_float4(o.x, o.y, o.z, 3.0e38f);
+        rp[1] = make_float4(d.x, d.y, d.z, 0.0f);
+      } else {
+        const float4 r0 = rp[0], r1 = rp[1];
+        ray_bad = !ray_query_valid(f3(r0.x, r0.y, r0.z), f3(r1.x, r1.y, r1.z), r0.w);
+        o = ray_bad ? f3(0, 0, 0) : f3(r0.x, r0.y, r0.z);
+        d = ray_bad ? f3(0, 0, 1) : f3(r1.x, r1.y, r1.z);
+        tmax = ray_bad ? 0.0f : fminf(r0.w, 3.0e38f);
+      }
+      trav_init(t, o, d, tmax, false);
+      return box_hit(t, P.root_lo, P.root_hi) && !ray_bad;
+    } else {
+      float3 o;
+      pinhole(o);
+      trav_init(t, o, d, 3.0e38f, false);
+      if (STATS) n_cam++;
+      if (DBG && pix_index(pix) == P.dbg_pix) printf("pixel (%d,%d) sample %d o=(%.9g %.9g %.9g) d=(%.9g %.9g %.9g)\n", px, py, sample, t.o.x, t.o.y, t.o.z, d.x, d.y, d.z);
+      return box_hit(t, P.root_lo, P.root_hi);
+    }
   };
 
   // A shadow ray ended (`done`) with what follows it already settled: add the
@@ -949,6 +1029,7 @@ __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_PER_SIMD) void render_kernel
     tr.node = fo ? 0 : tr.node;
     tr.sp = fo ? 0 : tr.sp;
     tr.tmax = fo ? 3.0e38f : tr.tmax;
+    if constexpr (RAYS) tr.tmax = fo ? park_tmax : tr.tmax;  // (a parked camera ray keeps the caller's bound)
     tr.prim = fo ? -1 : tr.prim;
     tr.found = fo ? false : tr.found;
   };
@@ -1193,6 +1274,7 @@ __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_PER_SIMD) void render_kernel
             if (emitted) {  // (only Diffuse emits shadow rays, so tr.d above was never read)
               hp = bo;      // the bounce ray waits in (hp, ns) behind the shadow ray in tr
               ns = v;
+              if constexpr (RAYS) park_tmax = 3.0e38f;
               shadow = SH_FOLLOW;
             } else {
               trav_init(tr, bo, v, 3.0e38f, false);
@@ -1413,6 +1495,7 @@ __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_PER_SIMD) void render_kernel
           if (shadow) {
             hp = cr.o;
             ns = cd;
+            if constexpr (RAYS) park_tmax = cr.tmax;  // (the first segment's bound travels with the parked ray)
             if (shadow == SH_STORE) shadow = SH_STORE_FOLLOW;
           }
           mode = M_TRAV;
@@ -1426,7 +1509,7 @@ __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_PER_SIMD) void render_kernel
         // where trace_ray's order is (acc + pend) + env -- one reordered
         // float addition at silhouettes against the map, inside the
         // near-exact tolerance; parking such rays instead cost C5 18%.)
-        if (ENV) {
+        if (ENV && !(RAYS && ray_bad)) {  // (RAYS: an invalid ray never reaches the map lookup)
           const float3 e = env_dir(P, cd);
           if (shadow == SH_STORE) ng = ng + e;
           else acc = acc + e;
@@ -1495,6 +1578,7 @@ __global__ __launch_bounds__(PT_BLOCK, PT_MIN_WAVES_PER_SIMD) void render_kernel
         }
         if (owner) {
           trav_init(tr, hp, ns, 3.0e38f, false);
+          if constexpr (RAYS) tr.tmax = park_tmax;
           shadow = 0;
           hl = h_lane;
         }
@@ -1908,9 +1992,6 @@ __global__ __launch_bounds__(PT_BLOCK) void features_kernel(FeatArgs A) {
   A.feat[(size_t)A.W * (size_t)A.H + p] = r1;
 }
 
-// Not finite: the exponent field is all ones (inf or NaN).
-__device__ __forceinline__ bool not_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-
 // Ray queries from device memory (ptgpu.h: pt_trace_rays_device): one lane per
 // ray, one wave per workgroup, the grid bounded -- wave b takes the chunks of
 // 64 rays b, b + grid, b + 2 * grid, ..., so the spill area is the grid's, not
@@ -1947,14 +2028,7 @@ __global__ __launch_bounds__(PT_BLOCK) void trace_kernel(TraceArgs A) {
     }
     const float3 o = f3(r0.x, r0.y, r0.z), d = f3(r1.x, r1.y, r1.z);
     const float tmax = fminf(r0.w, 3.0e38f);
-    bool valid = r0.w > 0.0f;  // (false for a NaN)
-    valid &= !(not_finite(o.x) || not_finite(o.y) || not_finite(o.z) || not_finite(d.x) || not_finite(d.y) || not_finite(d.z));
-    valid &= !(d.x == 0.0f && d.y == 0.0f && d.z == 0.0f);
-    {
-      Trav probe;  // o * (1 / d) as the node step forms it
-      trav_init(probe, o, d, tmax, OCC);
-      valid &= !(not_finite(o.x * probe.inv.x) && not_finite(o.y * probe.inv.y) && not_finite(o.z * probe.inv.z));
-    }
+    const bool valid = ray_query_valid(o, d, r0.w);
     Hit h;
     h.t = 0;
     h.prim = -1;
@@ -2017,7 +2091,9 @@ template <bool ENV, bool GTAB>
 static void launch_render(const KParams* P, int waves, bool stats, bool ref_counts, hipStream_t s) {
   const int grid = waves;  // one wave per workgroup
   const dim3 blk(PT_BLOCK);
-  if (ref_counts)
+  if (P->rays)  // a ray launch (host: no counters, no frame batch, no pixel trace)
+    hipLaunchKernelGGL((ptk::render_kernel<false, false, false, ENV, GTAB, false, false, true>), dim3(grid), blk, 0, s, *P);
+  else if (ref_counts)
     hipLaunchKernelGGL((ptk::render_kernel<true, false, true, ENV, GTAB>), dim3(grid), blk, 0, s, *P);
   else if (P->dbg_pix >= 0)
     hipLaunchKernelGGL((ptk::render_kernel<false, true, false, ENV, GTAB>), dim3(grid), blk, 0, s, *P);
@@ -2054,6 +2130,15 @@ extern "C" hipError_t ptk_render_occupancy_env(int* waves_per_cu, bool gtab) {
                             &blocks, ptk::render_kernel<false, false, false, true, true>, PT_BLOCK, 0)
                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(
                             &blocks, ptk::render_kernel<false, false, false, true, false>, PT_BLOCK, 0);
+  *waves_per_cu = blocks;
+  return e;
+}
+extern "C" hipError_t ptk_render_occupancy_rays_env(int* waves_per_cu, bool gtab) {
+  int blocks = 0;
+  hipError_t e = gtab ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                            &blocks, ptk::render_kernel<false, false, false, true, true, false, false, true>, PT_BLOCK, 0)
+                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                            &blocks, ptk::render_kernel<false, false, false, true, false, false, false, true>, PT_BLOCK, 0);
   *waves_per_cu = blocks;
   return e;
 }
@@ -2170,5 +2255,17 @@ extern "C" hipError_t ptk_render_occupancy(int* waves_per_cu, bool stats, bool e
   if (env) return ptk_render_occupancy_env(waves_per_cu, gtab);
   if (stats) return occupancy<true, false, false>(waves_per_cu);
   return gtab ? occupancy<false, false, true>(waves_per_cu) : occupancy<false, false, false>(waves_per_cu);
+}
+// The same of the RAYS builds (ray launches size their grid by their own kernels' figure).
+extern "C" hipError_t ptk_render_occupancy_rays_env(int* waves_per_cu, bool gtab);
+extern "C" hipError_t ptk_render_occupancy_rays(int* waves_per_cu, bool env, bool gtab) {
+  if (env) return ptk_render_occupancy_rays_env(waves_per_cu, gtab);
+  int blocks = 0;
+  hipError_t e = gtab ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                            &blocks, ptk::render_kernel<false, false, false, false, true, false, false, true>, PT_BLOCK, 0)
+                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                            &blocks, ptk::render_kernel<false, false, false, false, false, false, false, true>, PT_BLOCK, 0);
+  *waves_per_cu = blocks;
+  return e;
 }
 #endif  // PT_ENV_TU

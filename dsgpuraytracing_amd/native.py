@@ -26,6 +26,7 @@ PT_FLAG_STATS = 1
 PT_FLAG_REF_COUNTS = 2
 PT_FLAG_PACKED = 4
 PT_FLAG_PACKED16 = 8
+PT_FLAG_RAYS_CAPTURE = 16  # pt_render_rays*: generate, store and render the camera rays (spp 1)
 PT_MAX_FRAMES = 8  # frames per pt_render_frames_device launch (include/ptgpu.h)
 PT_TRACE_CLOSEST, PT_TRACE_OCCLUDED = 0, 1  # modes of pt_trace_rays*
 
@@ -187,6 +188,9 @@ _SIGS = {
     "pt_trace_rays": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_int32]),
     "pt_camera_rays_device": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p, c_void_p]),
     "pt_get_trace_info": (c_int32, [c_void_p, POINTER(pt_trace_info)]),
+    "pt_render_rays_device": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p, c_void_p, c_void_p, c_uint32]),
+    "pt_render_rays": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p, c_void_p, c_uint32]),
+    "pt_film_add_pass_rays": (c_int32, [c_void_p, POINTER(pt_tile), c_int32, c_void_p, c_void_p]),
     "pt_denoise_params_default": (c_int32, [POINTER(pt_denoise_params)]),
     "pt_denoise_device": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(pt_denoise_params), c_void_p,
                                     c_void_p]),

@@ -381,6 +381,53 @@ class Device:
         out[...] = t.cpu().numpy()
         return out
 
+    def render_rays(self, rays, tiles=None, out=None, capture: bool = False, stream: int = 0):
+        """Path-traces the caller's rays (pt_render_rays*): pixel p = x + y * W
+        of the frame of the last set_params follows row p of `rays`, an
+        (H * W, 8) float32 ray buffer as trace_rays takes it and camera_rays
+        writes it, with the params' spp, depth, seed and sample_base; returns
+        the (H, W, 3) float32 radiance, written inside `tiles` (the whole frame
+        by default) only.  capture=True (spp 1): the camera's rays of sample
+        sample_base are generated, written into `rays` and rendered -- the
+        image is render_tiles_device's.
+
+        A numpy `rays` goes through the host call, which waits (a capture
+        writes the array in place; `out` is a numpy array or a new one); a
+        torch device tensor through the device call, queued on `stream`
+        (default: torch's current stream), `out` a device tensor or a new,
+        zeroed one."""
+        hw = getattr(self, "_frame", None)
+        if hw is None:
+            raise ValueError("render_rays: set_params first")
+        h, w = hw
+        keep, arr = self._tiles(tile_fifo(w, h) if tiles is None else tiles)
+        flags = native.PT_FLAG_RAYS_CAPTURE if capture else 0
+        if hasattr(rays, "data_ptr"):
+            import torch
+            if (not rays.is_cuda or rays.device.index != self.device or rays.dtype != torch.float32
+                    or tuple(rays.shape) != (h * w, 8) or not rays.is_contiguous()):
+                raise ValueError(f"render_rays: need a contiguous float32 tensor of shape {(h * w, 8)} on device "
+                                 f"{self.device}")
+            if out is None:
+                out = torch.zeros((h, w, 3), dtype=torch.float32, device=rays.device)
+            elif (not hasattr(out, "data_ptr") or out.device != rays.device or out.dtype != torch.float32
+                  or tuple(out.shape) != (h, w, 3) or not out.is_contiguous()):
+                raise ValueError(f"render_rays: out must be a contiguous float32 tensor of shape {(h, w, 3)} on "
+                                 f"{rays.device}")
+            self._on_torch_stream(rays.device, stream, lambda s: check(self._lib.pt_render_rays_device(
+                self.handle, arr, len(keep), ctypes.c_void_p(rays.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                ctypes.c_void_p(s), flags)))
+            return out
+        if (not isinstance(rays, np.ndarray) or rays.dtype != np.float32 or rays.shape != (h * w, 8)
+                or not rays.flags.c_contiguous or (capture and not rays.flags.writeable)):
+            raise ValueError(f"render_rays: need a C-contiguous float32 array of shape {(h * w, 8)}")
+        if out is None:
+            out = np.zeros((h, w, 3), np.float32)
+        else:
+            self._check_frame(out, 3, np.float32, "render_rays")
+        check(self._lib.pt_render_rays(self.handle, arr, len(keep), rays.ctypes.data, out.ctypes.data, flags))
+        return out
+
     def trace_info(self) -> dict:
         """pt_get_trace_info: {rays, hits, invalid, trace_ms} of the last trace (waits for it)."""
         i = native.pt_trace_info()
@@ -465,6 +512,18 @@ class Film:
         index and accumulate them (pt_film_add_pass); returns once queued."""
         keep, arr = Device._tiles(tiles)
         check(self._lib.pt_film_add_pass(self.handle, arr, len(keep), ctypes.c_void_p(stream or None)))
+
+    def add_pass_rays(self, rays, tiles, stream: int = 0):
+        """add_pass with the pass rendered by replay of `rays` (pt_film_add_pass_rays):
+        a contiguous (H * W, 8) float32 device tensor (anything with data_ptr())
+        as Device.render_rays takes it; returns once queued."""
+        if not hasattr(rays, "data_ptr"):
+            raise ValueError("add_pass_rays: the rays are a device tensor")
+        if (tuple(rays.shape) != (self.height * self.width, 8) or rays.element_size() != 4 or not rays.is_contiguous()):
+            raise ValueError(f"add_pass_rays: need a contiguous float32 tensor of shape {(self.height * self.width, 8)}")
+        keep, arr = Device._tiles(tiles)
+        check(self._lib.pt_film_add_pass_rays(self.handle, arr, len(keep), ctypes.c_void_p(rays.data_ptr()),
+                                              ctypes.c_void_p(stream or None)))
 
     def resolve(self, hdr: bool = True, rgba: bool = True, err: bool = True):
         """(hdr (H, W, 3) float32, rgba (H, W, 4) uint8, err (H, W) float32) of
@@ -714,6 +773,29 @@ def _packed_flag(packed) -> int:
     if not packed:
         return 0
     return native.PT_FLAG_PACKED16 if _slot(packed) == 16 else native.PT_FLAG_PACKED
+
+
+def probe_rays(origin, w: int, h: int) -> np.ndarray:
+    """The (h * w, 8) float32 rays of a lat-long probe at `origin`, in the
+    environment map's own parameterisation (EnvironmentLight::sample_dir, as
+    the kernel's env_dir reads a map): ray p = x + y * w looks along the centre
+    of texel (x, y) of a w x h map, row 0 = +y, theta = (y + 0.5) / h * pi
+    from +y, phi = (x + 0.5) / w * 2 pi, d = (-sin theta sin phi, cos theta,
+    sin theta cos phi), tmax = +inf.  So the (h, w, 3) radiance
+    Device.render_rays returns for these rays IS that map, row 0 on top as
+    image_io.write_exr takes it: saved and loaded as the scene's environment
+    light, a miss along d looks up what the probe saw along d."""
+    y, x = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
+    theta = (y + 0.5) / h * np.pi
+    phi = (x + 0.5) / w * 2.0 * np.pi
+    d = np.stack([-np.sin(theta) * np.sin(phi), np.cos(theta), np.sin(theta) * np.cos(phi)], -1)
+    rays = np.zeros((h, w, 8), np.float32)
+    rays[..., 0:3] = np.asarray(origin, np.float64).reshape(3)
+    rays[..., 3] = np.inf
+    d32 = d.astype(np.float32)
+    d32 /= np.linalg.norm(d32.astype(np.float64), axis=-1, keepdims=True).astype(np.float32)
+    rays[..., 4:7] = d32
+    return rays.reshape(h * w, 8)
 
 
 def tile_fifo(w: int, h: int, tile: int = TILE) -> List[Tuple[int, int, int, int]]:

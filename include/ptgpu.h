@@ -53,6 +53,9 @@
  *   pt_trace_rays* / pt_camera_rays_device   BVHAccel::intersect (src/bvh.cpp:331-362) for rays
  *                               and results in device memory, in stream order: closest-hit
  *                               records or occlusion bits; the feature pass's camera rays
+ *   pt_render_rays* / pt_film_add_pass_rays   no counterpart: PathTracer::trace_ray
+ *                               (pathtracer.cpp:415-553) along the caller's rays instead of
+ *                               Camera::generate_ray's; the rays a render's samples took
  *   pt_denoise_* / pt_film_denoise*   no counterpart: an edge-avoiding filter of the film's mean,
  *                               guided by those records and the film's variance
  *   pt_reproject_* / pt_film_reproject   no counterpart: the film kept across a camera move, its
@@ -648,6 +651,61 @@ int pt_camera_rays_device(pt_ctx* ctx, const pt_tile* tiles, int32_t n_tiles, vo
 /* Of the context's last trace (all zero before the first, and after one of
  * n == 0); waits for it. */
 int pt_get_trace_info(pt_ctx* ctx, pt_trace_info* out);
+
+/* ---- Path tracing along the caller's rays (no reference counterpart: the
+ * reference's radiance loop, PathTracer::trace_ray pathtracer.cpp:415-553, is
+ * only reachable through Camera::generate_ray).  The third ray query: after
+ * "what does this ray hit" and "is it occluded", "what radiance arrives along
+ * it" -- light probes, lightmap texels, other camera models, an environment map
+ * baked from inside a scene.
+ *
+ * rays_dev holds width*height rays in pt_trace_rays_device's layout, ray p at
+ * ray[2p], p = x + y*W: exactly what pt_camera_rays_device writes.  Frame size,
+ * spp, max_depth, ns_area_light, seed and sample_base are the context's
+ * pt_params; the output and the tiles are pt_render_tiles_device's (W*H*3
+ * floats, only pixels inside the tiles are written).
+ *
+ * Replay (flags == 0): every sample k = 0 .. spp-1 of pixel p follows ray p.
+ * Its random stream is the camera path's, keyed by (seed, p, sample_base + k);
+ * the two jitter draws are taken and discarded, so every later draw has the
+ * dimension it has on the camera path.  o and d are used as given (d of unit
+ * length: the caller's contract, as pt_trace_rays').  tmax is clamped to
+ * 3.0e38 and bounds the FIRST segment only: when nothing is hit inside it the
+ * sample is a miss -- it sees the environment map if there is one, else
+ * nothing.  A ray that pt_trace_rays* calls INVALID (a component not finite, a
+ * zero direction, tmax NaN or <= 0, o over d overflowing on all three axes) is
+ * never traversed and every one of its samples contributes exactly 0, with an
+ * environment light too.  No screen-footprint cull applies, and the context's
+ * camera plays no part: replay needs a scene and params only.
+ *
+ * Capture (PT_FLAG_RAYS_CAPTURE; spp must be 1): the same kernel generates
+ * each pixel's ray as pt_render_tiles_device does for sample sample_base,
+ * stores {o, 3.0e38} and {d, 0} into rays_dev and renders it: the image is
+ * pt_render_tiles_device's bit for bit, the rays are the ones its samples
+ * took, and a replay of them gives the same image again.  Rays of pixels
+ * outside the tiles are left alone.
+ *
+ * PT_E_INVALID, nothing launched: a NULL context or buffer, n_tiles < 0, a
+ * flag other than 0 / PT_FLAG_RAYS_CAPTURE, capture with spp != 1, a ray
+ * buffer that overlaps the output.  PT_E_NOSCENE before pt_upload_scene or
+ * pt_set_params, and for a capture before pt_set_camera.
+ *
+ * Stream semantics are pt_render_tiles_device's, and the rays are READ in
+ * `stream` order too: after everything queued on `stream` before the call
+ * (the render kernel, on a stream of the context's, waits for it).  Captured
+ * rays and the image are complete in `stream` order. */
+#define PT_FLAG_RAYS_CAPTURE 16u
+int pt_render_rays_device(pt_ctx* ctx, const pt_tile* tiles, int32_t n_tiles, void* rays_dev, float* hdr_out_dev,
+                          void* stream, uint32_t flags);
+/* The same from and into host buffers (the rays are written back after a
+ * capture): stages, waits. */
+int pt_render_rays(pt_ctx* ctx, const pt_tile* tiles, int32_t n_tiles, void* rays_host, float* hdr_out_host,
+                   uint32_t flags);
+/* pt_film_add_pass with the pass rendered by replay of rays_dev: the same
+ * sample numbering, accumulation and refusals (and a NULL ray buffer, or one
+ * that overlaps the film's pass buffer: PT_E_INVALID).  A film may mix camera
+ * passes and ray passes. */
+int pt_film_add_pass_rays(pt_film* film, const pt_tile* tiles, int32_t n_tiles, const void* rays_dev, void* stream);
 
 /* ---- Denoiser: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010)
  * guided by the feature records and, as the spatial pass of SVGF, by the
