@@ -20,6 +20,7 @@ from dsgpuraytracing_amd import native
 from dsgpuraytracing_amd.pathtracer import Device, Scene
 from tests import bvh_check as bc
 from tests import lbvh_scenes as ls
+from tests.deep_trees import PT_STACK
 from tests.oracle_helpers import golden
 
 pytestmark = pytest.mark.gpu
@@ -126,12 +127,15 @@ def test_staircase_deepest_chain(dev, monkeypatch):
     restructuring) is a 30-deep chain of single-primitive leaves, three of
     them and the rest of the chain per 4-wide node.  Reported stack, as
     measured on an MI355X: 31 over 11 nodes with PT_LBVH_PASSES=0, 12 over 12
-    nodes with the default three passes.  31 is beyond PT_STACK = 24, so the
-    2048 rays of the first case run the traversal's spill path on a GPU-built
-    tree; that it does is printed, not asserted."""
+    nodes with the default three passes.  31 is beyond PT_STACK = 24: the
+    bound is asserted.  The 2048 rays themselves stay far below it (their
+    highest stack is 3: the leaves lie along three lines, and a straight ray
+    meets the boxes of one); tests/test_gpu_deep_trees.py runs the spill path
+    over a GPU-built chain whose leaves a ray can enter all at once."""
     t0 = _check_case(dev, monkeypatch, ls.scene("staircase"), passes=0)
     t3 = _check_case(dev, monkeypatch, ls.scene("staircase"))
     print(f"staircase: stack {t0['info']['bvh_stack']} (passes 0), {t3['info']['bvh_stack']} (default)")
+    assert t0["info"]["bvh_stack"] > PT_STACK
 
 
 @pytest.mark.parametrize("lo,hi,short", [(0.1, 0.7, False), (0.1, 0.8, True), (0.4, 0.6, True)])

@@ -583,6 +583,13 @@ def test_hip_deep_bvh_stack_spill_vs_restatement(monkeypatch, restate, tmp_path)
     img2 = np.zeros((64, 64, 3), np.float32)
     dev.render_tiles([(0, 0, 64, 64)], img2)
     assert np.array_equal(img, img2)
+    monkeypatch.delenv("PT_NO_TRI_ONLY")
+    # the spill path really ran: lane-steps with entries beyond PT_STACK, counted by the STATS build
+    img3 = np.zeros((64, 64, 3), np.float32)
+    dev.render_tiles([(0, 0, 64, 64)], img3, stats=True)
+    st = dev.stats()
+    assert st["counters_valid"] == 1 and st["deep_stack_steps"] > 0
+    assert np.array_equal(img, img3)
     rh, rt, rp, _, ra = restate.intersect(path, o.reshape(-1), dr.reshape(-1), maxt)
     assert hit.mean() > 0.3 and np.array_equal(hit, rh)
     both = hit == 1
